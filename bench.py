@@ -64,7 +64,45 @@ def parse():
     ap.add_argument("--no-dp-evidence", action="store_true",
                     help="N > 1: skip the default self-verification block of the JSON line (device identities, linearity check of the "
                          "exchange, replica checksums, all-reduce timing)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: its per-sample losses, "
+                         "the clip statistics, and a fixed seeded sample of the parameters, EMA and AdamW moments")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20            # --dump-outputs: elements drawn from each state arena (4 arenas x 4 MB + an 8 MB index: 24 MB in all)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def capture_outputs(runner, out):
+    """What the last timed step handed its caller, copied to host arrays right after the timed region (later work reuses the buffers):
+    the per-sample losses and clip statistics step() returns, and the state it updated in place -- parameters, EMA and both AdamW
+    moments -- at DUMP_SAMPLE positions of the trainable arena drawn by a fixed seed (the same positions on every run of a config)."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items() if k != "stats" and torch.is_tensor(v)}
+    arrays["clip_stats"] = out["stats"].detach().float().cpu().numpy()
+    runner.sync_sweep()
+    nt = runner.model.engine.n_trainable
+    idx = torch.randint(0, nt, (min(DUMP_SAMPLE, nt),), generator=torch.Generator().manual_seed(0)).sort().values
+    dev_idx = idx.to(runner.ema.device)
+    arrays["state_sample_index"] = idx.double().numpy()
+    for name, arena in (("params", runner.opt.p), ("ema", runner.ema[:nt]), ("adam_exp_avg", runner.opt.m),
+                        ("adam_exp_avg_sq", runner.opt.v)):
+        arrays[f"{name}_sample"] = arena.index_select(0, dev_idx).float().cpu().numpy()
+    return arrays
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte cap")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": sorted(n + ".npy" for n in arrays), "bytes": total}
 
 
 def host_cores():
@@ -471,6 +509,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = tt.item()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = write_outputs(args.dump_outputs, capture_outputs(runner, out))
 
     runner.guard.poll(block=True)               # NaN / Inf loss or gradient norm, bad labels: raises (non-zero exit)
     loss_ok = bool(torch.isfinite(out["remain_mse"]).all().item() and torch.isfinite(out["forget_mse"]).all().item())
@@ -595,7 +636,7 @@ def main():
             "step_tflops_per_gpu": step_flops / (ms_per_step * 1e-3) / 1e12,
             "step_frac_of_bf16_mfma_peak": step_flops / (ms_per_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
             "dp_overlap": dp_overlap, "grad_transport": runner.grad_transport if world > 1 else None, "check": check_res,
-            "world_size": world, "dp": dp_ev,
+            "world_size": world, "dp": dp_ev, **({"dump_outputs": dumped} if dumped else {}),
             "roofline": {"bound": "mfma",
                          "kernel": "k_gemm_pipe<4,2,3,6,true,true,1,2,2,false,4> = 192x192 tile, three LDS slots, eight multiplying waves + four loader waves "
                                    "that issue the LDS-DMA: the weight "

@@ -652,6 +652,25 @@ def gen_sampling(ref_models, ref_diffusion):
     torch.manual_seed(5)
     one = d.p_sample(stub, z, torch.tensor([0, 9, 3, 0]), clip_denoised=False, model_kwargs={})
     out["one_sample_seed5"] = one["sample"].numpy(); out["one_pred_xstart"] = one["pred_xstart"].numpy()
+    # the same runs with z and A in float64 (the tables and timesteps as the reference casts them): what tests/test_oracle_golden.py
+    # compares the CPU oracle with.  In float32 ten steps amplify the CPU's own last-bit rounding of exp / log / sqrt (torch's MKL
+    # vector-math path differs between CPU vendors) past 1e-6; in float64 that difference stays far below it
+    z64, A64 = z.double(), A.double()
+    stub64 = lambda x, ts, **kw: torch.einsum("oc,nchw->nohw", A64, x) * torch.cos(ts.float() / 300.0).view(-1, 1, 1, 1) + 0.05
+
+    def stub2_64(x, ts, **kw):
+        lin = torch.einsum("oc,nchw->nohw", A64, x)
+        eps = 0.9 * x / s1m[ts].view(-1, 1, 1, 1) + 0.02 * lin[:, :C]
+        return torch.cat([eps, lin[:, C:] * torch.cos(ts.float() / 300.0).view(-1, 1, 1, 1) + 0.05], dim=1)
+    for clip in (True, False):
+        torch.manual_seed(77)
+        out[f"f64_stub_clip{int(clip)}"] = d.p_sample_loop(stub64, z64.shape, z64, clip_denoised=clip, model_kwargs={}, device="cpu").numpy()
+    torch.manual_seed(77)
+    out["f64_stub2_clip0"] = d.p_sample_loop(stub2_64, z64.shape, z64, clip_denoised=False, model_kwargs={}, device="cpu").numpy()
+    torch.manual_seed(5)
+    one = d.p_sample(stub64, z64, torch.tensor([0, 9, 3, 0]), clip_denoised=False, model_kwargs={})
+    out["f64_one_sample_seed5"] = one["sample"].numpy(); out["f64_one_pred_xstart"] = one["pred_xstart"].numpy()
+    assert all(out[k].dtype == np.float64 for k in out if k.startswith("f64_"))
     # the real model + classifier-free guidance, 5 steps
     m = ref_models.DiT(**TINY)
     m.load_state_dict(tiny_weights())
@@ -691,6 +710,14 @@ def gen_ddpm_sampler():
         torch.manual_seed(13)
         xs, x0s = den.generalized_steps_conditional(x, c, seq, model, b, cond_scale=2.0, eta=eta)
         out[f"last_eta{eta}"] = xs[-1].numpy(); out[f"x0_first_eta{eta}"] = x0s[0].numpy(); out[f"x_mid_eta{eta}"] = xs[5].numpy()
+    # x, A and the betas in float64: the CPU oracle's fixture (see gen_sampling)
+    A64 = A.double()
+    model64 = lambda xt, t, cc, cond_scale=3.0, mode="test": torch.einsum("oc,nchw->nohw", A64, xt) * torch.cos(t / 300.0).view(-1, 1, 1, 1) + 0.01 * cc.view(-1, 1, 1, 1) * cond_scale
+    for eta in (0.0, 0.5):
+        torch.manual_seed(13)
+        xs, x0s = den.generalized_steps_conditional(x.double(), c, seq, model64, b.double(), cond_scale=2.0, eta=eta)
+        assert xs[-1].dtype == torch.float64
+        out[f"f64_last_eta{eta}"] = xs[-1].numpy(); out[f"f64_x0_first_eta{eta}"] = x0s[0].numpy(); out[f"f64_x_mid_eta{eta}"] = xs[5].numpy()
     out["alpha_t"] = den.compute_alpha(b, torch.tensor([0, 999, 500])).flatten().numpy()
     out["alpha_m1"] = den.compute_alpha(b, torch.tensor([-1])).flatten().numpy()
     np.savez_compressed(os.path.join(HERE, "ddpm_sampler.npz"), **out)

@@ -88,3 +88,54 @@ def test_watchdog_stays_quiet_when_rearmed_and_stopped():
     """)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "done" in r.stdout and "watchdog" not in r.stderr
+
+
+def test_steps_below_one_is_refused(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        bench.parse()
+    except SystemExit as e:
+        assert e.code == 2
+    else:
+        raise AssertionError("--steps 0 accepted")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.steps == 3 and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_step_within_the_cap(tmp_path):
+    """--dump-outputs on a stand-in runner (CPU tensors): every array is float32 / float64, the state sample is drawn at the same seeded
+    positions on every call, and the whole dump stays under the cap."""
+    sys.path.insert(0, ROOT)
+    import types
+
+    import numpy as np
+    import torch
+    import bench
+    nt = 3_000_000
+    g = torch.Generator().manual_seed(7)
+    p, m, v = (torch.randn(nt, generator=g) for _ in range(3))
+    ema = torch.randn(nt + 10, generator=g)
+    runner = types.SimpleNamespace(opt=types.SimpleNamespace(p=p, m=m, v=v), ema=ema,
+                                   model=types.SimpleNamespace(engine=types.SimpleNamespace(n_trainable=nt)), sync_sweep=lambda: None)
+    out = {"forget_mse": torch.rand(4), "forget_vb": torch.rand(4), "remain_mse": torch.rand(4), "remain_vb": torch.rand(4),
+           "forget_sign": -1.0, "stats": torch.rand(4)}
+    a1 = bench.capture_outputs(runner, out)
+    a2 = bench.capture_outputs(runner, out)
+    info = bench.write_outputs(str(tmp_path / "dump"), a1)
+    assert info["bytes"] <= 64 << 20
+    want = {"forget_mse", "forget_vb", "remain_mse", "remain_vb", "clip_stats", "state_sample_index", "params_sample", "ema_sample",
+            "adam_exp_avg_sample", "adam_exp_avg_sq_sample"}
+    assert set(a1) == want and sorted(os.listdir(tmp_path / "dump")) == sorted(n + ".npy" for n in want)
+    for n in want:
+        x = np.load(tmp_path / "dump" / (n + ".npy"))
+        assert x.dtype in (np.float32, np.float64), n
+        np.testing.assert_array_equal(x, a2[n])
+    idx = a1["state_sample_index"].astype(np.int64)
+    assert idx.size == bench.DUMP_SAMPLE and idx.min() >= 0 and idx.max() < nt
+    np.testing.assert_array_equal(a1["params_sample"], p.numpy()[idx])
+    np.testing.assert_array_equal(a1["ema_sample"], ema.numpy()[idx])
+    np.testing.assert_array_equal(a1["adam_exp_avg_sq_sample"], v.numpy()[idx])
+    np.testing.assert_array_equal(a1["remain_mse"], out["remain_mse"].numpy())
