@@ -302,6 +302,44 @@ typedef struct sfron_fp8_gemm_desc {
 int sfron_fp8_gemm_supported(int M, int N, int K);
 int sfron_fp8_gemm(const sfron_fp8_gemm_desc* desc /* HOST pointer */, void* stream);
 
+/* fp8 BACKWARD (opt-in, sfron_aux_set_fp8_dgrad): the four input-gradient products dX[M][in] = dY[M][out] . W[out][in] of a DiT block on
+ * the same scaled MFMA.  dY is MX-scaled: one E8M0 scale byte per 32 consecutive elements of a row, [M][N / 32] beside the e4m3 [M][N]:
+ *   X    = ceil(log2(amax / 448)) over the 32 values (amax of their magnitudes), clamped to [-127, 127]; an all-zero block gets X = -127
+ *   byte = X + 127
+ *   code = e4m3fn_RNE(x * 2^-X)            (|x * 2^-X| <= 448: nothing saturates; x * 2^-X is exact in fp32)
+ * (for finite input; an infinite amax gets X = 127, and blocks holding a NaN are outside the rule)
+ * No global amax, no delayed-scaling state: every scale is local to its 32 values.  W is read as its TRANSPOSED e4m3 shadow [in][out] (the
+ * same codes and per-tensor scale as the forward shadow; sfron_fp8_transpose_shadow), one scale of 1 per block, its tensor scale undone in
+ * the epilogue. */
+/* bf16 src [M][N] -> MX e4m3 dst [M][N] + scales [M][N / 32] by the rule above; N % 32 == 0 */
+int sfron_cast_mx8(const uint16_t* src, int M, int N, uint8_t* dst, uint8_t* scales, void* stream);
+/* e4m3 weight shadow -> transposed copy, one launch for n_matrices matrices: table = DEVICE int64 [n_matrices][4] rows (src_off, dst_off,
+ * R, C), w8t[dst_off + c * R + r] = w8[src_off + r * C + c].  Offsets, R and C multiples of 8 (a row that is not is skipped). */
+int sfron_fp8_transpose_shadow(const uint8_t* w8, uint8_t* w8t, const int64_t* table, int n_matrices, void* stream);
+/* C[M][N] = (A[M][K] with its MX scales) . B[N][K]^T / *w_scale, B = the transposed shadow of W, with
+ *   SFRON_EPI_BF16      c_bf16 = result                                                        (qkv, proj, fc1 dgrads)
+ *   SFRON_EPI_DGELU     r = result * gelu_tanh'(aux: bf16 pre-activation [M][ldaux])           (fc2 dgrad)
+ *   SFRON_EPI_DGELU_Q   r = result * decode(aux: uint8 GELU' codes [M][ldaux], SFRON_EPI_GELU_Q)
+ *                       for both: c_bf16 = bf16(r); c_e4m3 [M][N] + c_scales [M][N / 32] = the MX form of the bf16-ROUNDED c_bf16 (equal to
+ *                       sfron_cast_mx8(c_bf16) bit for bit); col_partials (or NULL) fp32 [M / 256][N]: row t = column sums of r over
+ *                       output rows 256 t .. 256 t + 255 (sum them with sfron_reduce_chunks)
+ * Shapes as sfron_fp8_gemm_supported; the DGELU forms need N % 128 == 0.  tile_hint: 0 = auto, 8 = 256 x 128, 9 = 256 x 144 tiles. */
+typedef struct sfron_fp8_dgrad_desc {
+  const uint8_t* A;                  /* MX e4m3 dY [M][K] */
+  const uint8_t* a_scales;           /* its E8M0 bytes [M][K / 32] */
+  const uint8_t* B;                  /* transposed e4m3 weight [N][K] */
+  int M, N, K;
+  const float* w_scale;              /* DEVICE scalar: the scale W was quantised with */
+  int epilogue;
+  uint16_t* c_bf16; int ldc_bf16;
+  const uint16_t* aux; int ldaux;
+  uint8_t* c_e4m3;
+  uint8_t* c_scales;
+  float* col_partials;
+  int tile_hint;
+} sfron_fp8_dgrad_desc;
+int sfron_fp8_dgrad(const sfron_fp8_dgrad_desc* desc /* HOST pointer */, void* stream);
+
 /* ------------------------------------------------------------------ convolutional U-Net blocks (conv.hip)
  * Replaces the Conv2d / GroupNorm / bmm-softmax sequences of DDPM/models/diffusion.py:43-192,283-413 (Conditional_Model) forward
  * and backward.  Activations are NHWC: a [batch * H * W][C] row-major matrix (bf16 where they feed a GEMM, fp32 elsewhere). */
@@ -743,6 +781,15 @@ int sfron_aux_wait_ada_factors(void* aux, void* stream);
  * backward pass -- a gradient exchange, a sweep -- and must pick a stream that does NOT share a hardware queue with these two: the runtime maps
  * streams onto four hardware queues and two streams on one queue serialise (profiles/r06_hw_queues.txt; the host mirror probes: streams.py). */
 int sfron_aux_streams(void* aux, void** side /* HOST out */, void** side2 /* HOST out */);
+/* Arms the handle for the fp8 backward: every sfron_dit_backward / _dp call through it then runs the four dgrads of each block on the fp8
+ * matrix core (sfron_fp8_dgrad) -- dY cast by sfron_cast_mx8 (d_br, d_br2, dqkv) or by the fc2 dgrad's epilogue (d_hpre); the weight
+ * gradients keep reading the bf16 tensors.  w8t: the transposed e4m3 shadow of the block weights, indexed like the block range of the arena
+ * (matrix j of block l at its arena offset minus the offset of block 0 rounded down to a multiple of 256); w_scales: fp32 [L][4] (qkv, proj, fc1, fc2), the forward pass's
+ * shadow scales; mx_workspace: sfron_dit_fp8_dgrad_workspace_bytes(cfg) bytes.  The caller keeps w8t equal to the transpose of the shadow
+ * the forward pass read.  w8t == NULL disarms.  A backward pass on an armed handle returns SFRON_ERR_UNSUPPORTED for shapes the fp8 tiles
+ * do not take. */
+int64_t sfron_dit_fp8_dgrad_workspace_bytes(const sfron_dit_cfg* cfg);
+int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales, void* mx_workspace);
 int sfron_aux_destroy(void* aux);
 
 #ifdef __cplusplus

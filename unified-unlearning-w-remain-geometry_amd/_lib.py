@@ -135,6 +135,20 @@ _PROTOS.update({
 })
 
 
+class Fp8DgradDesc(ctypes.Structure):
+    """Mirror of sfron_fp8_dgrad_desc."""
+    _fields_ = [("A", c_void_p), ("a_scales", c_void_p), ("B", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int), ("w_scale", c_void_p),
+                ("epilogue", c_int), ("c_bf16", c_void_p), ("ldc_bf16", c_int), ("aux", c_void_p), ("ldaux", c_int), ("c_e4m3", c_void_p),
+                ("c_scales", c_void_p), ("col_partials", c_void_p), ("tile_hint", c_int)]
+
+
+_PROTOS.update({
+    "sfron_cast_mx8": (c_int, [_P, c_int, c_int, _P, _P, _S]),
+    "sfron_fp8_transpose_shadow": (c_int, [_P, _P, _P, c_int, _S]),
+    "sfron_fp8_dgrad": (c_int, [POINTER(Fp8DgradDesc), _S]),
+})
+
+
 class BGemmDesc(ctypes.Structure):
     """Mirror of sfron_bgemm_desc."""
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int), ("lda", c_int), ("ldb", c_int),
@@ -245,6 +259,8 @@ _PROTOS.update({
     "sfron_dit_forward_phase": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _S]),
     "sfron_dit_forward_fp8_phase": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _S]),
     "sfron_dit_fp8_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
+    "sfron_dit_fp8_dgrad_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
+    "sfron_aux_set_fp8_dgrad": (c_int, [c_void_p, _P, _P, _P]),
     "sfron_dit_forward_fp8": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
     "sfron_probe_create": (c_int, [c_int, POINTER(c_void_p)]),
     "sfron_probe_reset": (c_int, [c_void_p]),

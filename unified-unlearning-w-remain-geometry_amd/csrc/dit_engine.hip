@@ -240,7 +240,8 @@ static int ablate_mask() {
 // ---- aux: a side stream + events so the weight-gradient GEMMs (which nothing downstream in the backward chain
 // depends on) run concurrently with the dgrad / elementwise chain and fill the CUs its tile counts leave idle
 struct Probe;
-struct Aux { hipStream_t side, side2; hipEvent_t produced[4], consumed[8], done, join2, ada_ready, ada_factors; Probe* probe; const uint8_t* sq_mask; double* sq_partials; int dev; };
+struct Aux { hipStream_t side, side2; hipEvent_t produced[4], consumed[8], done, join2, ada_ready, ada_factors; Probe* probe; const uint8_t* sq_mask; double* sq_partials; int dev;
+             const uint8_t* w8t; const float* w8_scales; char* mx_ws; };      // fp8 dgrads (sfron_aux_set_fp8_dgrad), w8t NULL = off
 
 // The two weight-gradient streams of a handle come from a per-device FREE LIST and go back to it when the handle is destroyed: a process
 // that builds one engine after another (bench.py's configuration legs, set_batch_size(), a test session) keeps running on the SAME
@@ -293,6 +294,12 @@ int sfron_aux_create(void** aux) {
   if (hipEventCreateWithFlags(&a->ada_ready, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
   if (hipEventCreateWithFlags(&a->ada_factors, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
   *aux = a;
+  return SFRON_OK;
+}
+int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales, void* mx_workspace) {
+  SFRON_CHECK_ARG(aux && (!w8t || (w_scales && mx_workspace)));
+  Aux* a = (Aux*)aux;
+  a->w8t = w8t; a->w8_scales = w8t ? w_scales : nullptr; a->mx_ws = w8t ? (char*)mx_workspace : nullptr;
   return SFRON_OK;
 }
 int sfron_aux_wait_ada(void* aux, void* stream) {
@@ -453,6 +460,24 @@ int sfron_dit_forward_phase(const sfron_dit_cfg* cfg, const float* params, const
                             void* const* block_ready, void* probe, int phase, void* stream) {
   SFRON_CHECK_ARG(phase >= 1 && phase <= 4);
   return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, probe, nullptr, stream, block_ready, phase);
+}
+
+// fp8 dgrads: two MX operands live at a time -- `a` (d_br / d_br2 / dqkv, each consumed by the launch after its cast) and `b` (d_hpre, written
+// by the fc2 dgrad while it reads `a`, consumed by the fc1 dgrad): e4m3 [M][width] + E8M0 [M][width / 32] each
+struct MxWs { uint8_t *a, *a_sc, *b, *b_sc; };
+static size_t mx_ws(const Dims& d, char* base, MxWs* m) {
+  size_t o = 0;
+  auto take = [&](size_t bytes) { char* r = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return (uint8_t*)r; };
+  const size_t wa = (size_t)3 * d.D, wb = (size_t)d.F;
+  uint8_t* a = take((size_t)d.M * wa); uint8_t* as = take((size_t)d.M * wa / 32);
+  uint8_t* b = take((size_t)d.M * wb); uint8_t* bs = take((size_t)d.M * wb / 32);
+  if (m) { m->a = a; m->a_sc = as; m->b = b; m->b_sc = bs; }
+  return o;
+}
+int64_t sfron_dit_fp8_dgrad_workspace_bytes(const sfron_dit_cfg* cfg) {
+  Dims d;
+  if (make_dims(cfg, d) != SFRON_OK) return -1;
+  return (int64_t)mx_ws(d, nullptr, nullptr);
 }
 
 int64_t sfron_dit_fp8_workspace_bytes(const sfron_dit_cfg* cfg) {
@@ -768,6 +793,23 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
   if (ax) { (void)hipEventRecord(ax->done, hs); (void)hipStreamWaitEvent(ax->side, ax->done, 0); }   // side starts after everything before us
   const int fc1_rows = (ablate_mask() & 64) ? 0 : sfron_gemm_dgelu_colpart_rows(M, d.F, D);    // 0: shape not on a 256-row pipelined tile -> column-sum launch
   const bool qkv_fused = !(ablate_mask() & 128) && sfron_attn_bwd_bias_supported(T);           // one-kernel attention backward (T = 128 / 256)
+  // fp8 dgrads (sfron_aux_set_fp8_dgrad): each dY is cast to MX e4m3 right after produced(i) -- the weight-gradient streams keep reading the
+  // bf16 tensor -- and consumed by the next launch on this stream, so one MX buffer per kind serves every block
+  const bool f8b = ax && ax->w8t;
+  MxWs mx{};
+  if (f8b) {
+    if (!sfron_fp8_gemm_supported(M, D, 3 * D) || !sfron_fp8_gemm_supported(M, D, D) || !sfron_fp8_gemm_supported(M, d.F, D) ||
+        !sfron_fp8_gemm_supported(M, D, d.F) || d.F % 128)
+      return SFRON_ERR_UNSUPPORTED;
+    (void)mx_ws(d, ax->mx_ws, &mx);
+  }
+  // dX [M x D] (bf16) = MX(dY) [M x N] . W [N x D] with W's transposed shadow (block-relative offset w_off) and scale
+  auto dgrad_fp8 = [&](const uint8_t* a, const uint8_t* a_sc, int64_t w_off, const float* wsc, int N, __bf16* dX) -> int {
+    sfron_fp8_dgrad_desc q{};
+    q.A = a; q.a_scales = a_sc; q.B = ax->w8t + (w_off - (P.blocks & ~255LL)); q.M = M; q.N = D; q.K = N; q.w_scale = wsc;
+    q.epilogue = SFRON_EPI_BF16; q.c_bf16 = (uint16_t*)dX; q.ldc_bf16 = D;
+    return sfron_fp8_dgrad(&q, stream);
+  };
 
   // ---- final layer
   RUN(sfron_patchify(d_out, B, d.Co, d.S, d.S, d.p, 1, (uint16_t*)w.d_tok, d.Po, stream));
@@ -831,8 +873,19 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
     // bf16 rounding); the side stream only adds the M / 256 partial rows (was: a second 75 MB pass over d_hpre per block)
     float* const bp_fc1 = w.bpart + (size_t)pl * fc1_rows * d.F;
     if (fc1_rows) g.col_partials = bp_fc1;
-    arm(1);
-    RUN(sfron_gemm_bf16(&g, stream));
+    const float* const wsc = f8b ? ax->w8_scales + (size_t)l * 4 : nullptr;        // qkv, proj, fc1, fc2
+    if (f8b) {
+      // the same product with MX(d_br) . fc2's transposed shadow; the epilogue also leaves MX(d_hpre) for the fc1 dgrad
+      RUN(sfron_cast_mx8((const uint16_t*)w.d_br[pl], M, D, mx.a, mx.a_sc, stream));
+      sfron_fp8_dgrad_desc q{};
+      q.A = mx.a; q.a_scales = mx.a_sc; q.B = ax->w8t + (pb + P.o_fc2_w - (P.blocks & ~255LL)); q.M = M; q.N = d.F; q.K = D; q.w_scale = wsc + 3;
+      q.epilogue = g.epilogue; q.c_bf16 = g.c_bf16; q.ldc_bf16 = d.F; q.aux = g.aux; q.ldaux = d.F;
+      q.c_e4m3 = mx.b; q.c_scales = mx.b_sc; q.col_partials = fc1_rows ? bp_fc1 : nullptr;
+      RUN(sfron_fp8_dgrad(&q, stream));
+    } else {
+      arm(1);
+      RUN(sfron_gemm_bf16(&g, stream));
+    }
     produced(1);
     if (delay_fc2) {
       sq_next = sq_slot(l, 3);
@@ -845,7 +898,8 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
       RUN(wgrad_side(w.d_hpre[pl], xmod2, d.F, D, grads + pb + P.o_fc1_w));
     } else RUN(wgrad_side(w.d_hpre[pl], xmod2, d.F, D, grads + pb + P.o_fc1_w, grads + pb + P.o_fc1_b));
     consumed(1, l);
-    RUN(dgrad_bf16(w.d_hpre[pl], wb + pb + P.o_fc1_w, d.F, w.d_xmod));
+    if (f8b) RUN(dgrad_fp8(mx.b, mx.b_sc, pb + P.o_fc1_w, wsc + 2, d.F, w.d_xmod));
+    else RUN(dgrad_bf16(w.d_hpre[pl], wb + pb + P.o_fc1_w, d.F, w.d_xmod));
     // ---- attention branch: x1 = x0 + gate_msa * proj(attn(qkv(xmod1)))
     before_overwrite(2, l);
     if (fuse) arm(2);
@@ -857,7 +911,10 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
       RUN(wgrad_side(w.d_br2[pl], o, D, D, grads + pb + P.o_proj_w));
       consumed(2, l);
     }
-    RUN(dgrad_bf16(w.d_br2[pl], wb + pb + P.o_proj_w, D, w.d_o));
+    if (f8b) {
+      RUN(sfron_cast_mx8((const uint16_t*)w.d_br2[pl], M, D, mx.a, mx.a_sc, stream));
+      RUN(dgrad_fp8(mx.a, mx.a_sc, pb + P.o_proj_w, wsc + 1, D, w.d_o));
+    } else RUN(dgrad_bf16(w.d_br2[pl], wb + pb + P.o_proj_w, D, w.d_o));
     before_overwrite(3, l);
     int proj_rc = SFRON_OK;
     auto proj_beside = [&]() {
@@ -893,7 +950,10 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
     if (block_events && block_events[l]) {                 // block l: the four weight gradients, qkv.bias and fc1.bias are final
       if (hipEventRecord((hipEvent_t)block_events[l], (hipStream_t)side) != hipSuccess) return (int)hipGetLastError();
     }
-    RUN(dgrad_bf16(w.dqkv[pl], wb + pb + P.o_qkv_w, 3 * D, w.d_xmod));
+    if (f8b) {
+      RUN(sfron_cast_mx8((const uint16_t*)w.dqkv[pl], M, 3 * D, mx.a, mx.a_sc, stream));
+      RUN(dgrad_fp8(mx.a, mx.a_sc, pb + P.o_qkv_w, wsc + 0, 3 * D, w.d_xmod));
+    } else RUN(dgrad_bf16(w.dqkv[pl], wb + pb + P.o_qkv_w, 3 * D, w.d_xmod));
     if (l > 0) {
       before_overwrite(0, l - 1);
       if (fuse) arm(0);                     // consumed by produced(0) at the top of block l - 1

@@ -9,8 +9,10 @@
 //   activations  are quantised where they are PRODUCED, with static power-of-two scales per kind: LayerNorm+modulate writes its
 //                bf16 output (the backward pass's operand) and the e4m3 copy, the fc1 epilogue writes h in bf16 and e4m3, the
 //                attention output gets one cast kernel.
-// The backward pass is unchanged (bf16 operands, bf16 weight shadow): the quantisation is a straight-through estimator, as in
-// oracle/fp8_ref.py.  e4m3 = OCP e4m3fn (gfx950's v_cvt_pk_fp8_f32), round to nearest even, saturating at +-448.
+// The backward pass keeps bf16 operands (the quantisation is a straight-through estimator, as in oracle/fp8_ref.py) unless the caller arms
+// the fp8 dgrads (sfron_aux_set_fp8_dgrad): the four input-gradient products of a block then multiply an MX-scaled e4m3 dY (one E8M0 scale
+// per 32 consecutive elements of a row, sfron_cast_mx8) by a TRANSPOSED copy of the e4m3 weight shadow (sfron_fp8_transpose_shadow) on the
+// same scaled MFMA, the dY scales fed per lane.  e4m3 = OCP e4m3fn (gfx950's v_cvt_pk_fp8_f32), round to nearest even, saturating at +-448.
 //
 // GEMM kernel: C[M][N] = deq * (A8[M][K] . B8[N][K]^T) with the 256 x 128 x 128-byte tile of tools/probes/fp8_gemm_probe.hip
 // (three LDS slots, both operands staged by buffer_load ... lds with the XOR swizzle on the source address, 8 waves of 32 x 128;
@@ -57,6 +59,24 @@ __device__ __forceinline__ uint32_t pack_e4m3(float a, float b, float c, float d
   v = __builtin_amdgcn_cvt_pk_fp8_f32(sat8(c), sat8(d), v, true);
   return (uint32_t)v;
 }
+
+// ---- MX (block-scaled) e4m3 of a dY operand: one E8M0 byte per 32 consecutive elements of a row (include/sfron.h states the rule).
+// X = ceil(log2(amax / 448)) from the exponent of amax: amax = f 2^e, f in [0.5, 1), 448 = 0.875 2^9 -> X = e - 9 if f <= 0.875, else e - 8
+// (exact: no division, no log); clamped to [-127, 127], an all-zero block gets -127, an infinite amax 127 (the clamp of +inf).  The element
+// is e4m3(x 2^-X): |x 2^-X| <= 448.  X <= 120 for any finite bf16 amax; 2^-X is built from its bits, 2^-127 as the subnormal it is.  Blocks
+// holding a NaN are outside the rule (fmaxf drops the NaN from amax; the NaN itself converts to an e4m3 NaN).
+__device__ __forceinline__ int mx_exp(float amax) {
+  if (!(amax > 0.f)) return -127;
+  if (isinf(amax)) return 127;
+  int e;
+  const float f = frexpf(amax, &e);
+  const int x = f <= 0.875f ? e - 9 : e - 8;
+  return x < -127 ? -127 : (x > 127 ? 127 : x);
+}
+__device__ __forceinline__ float mx_inv(int x) {                                                                  // 2^-x, x in [-127, 127]
+  return x < 127 ? __uint_as_float((uint32_t)(127 - x) << 23) : __uint_as_float(0x00400000u);
+}
+__device__ __forceinline__ float amax4v(f32x4 v) { return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))); }
 
 // ---------------------------------------------------------------- weights: per-tensor amax / quantisation
 struct TensorRange { long long off, n; };   // element range of one tensor inside the arena (off, n multiples of 8)
@@ -122,6 +142,63 @@ __global__ __launch_bounds__(TPB) void k_cast_e4m3_f32(const float* __restrict__
     reinterpret_cast<uint32_t*>(dst)[i] = pack_e4m3(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
   }
   amax_report(amax, 1, am);
+}
+
+// bf16 [n] (rows of N, N % 32 == 0: the flat index of a 32-block is its scale's index in [M][N / 32]) -> MX e4m3 + E8M0 bytes.  Eight elements
+// per lane, a block = the four lanes of a DPP quad (the grid-stride loop keeps quads together: n / 8 is a multiple of 4)
+__global__ __launch_bounds__(TPB) void k_cast_mx8(const __bf16* __restrict__ src, int64_t n, uint8_t* __restrict__ dst, uint8_t* __restrict__ sc) {
+  const int64_t n8 = n >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n8; i += (int64_t)gridDim.x * TPB) {
+    const bf16x8 v = reinterpret_cast<const bf16x8*>(src)[i];
+    const f32x4 a = {bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3])}, b = {bf2f(v[4]), bf2f(v[5]), bf2f(v[6]), bf2f(v[7])};
+    float am = fmaxf(amax4v(a), amax4v(b));
+    am = fmaxf(am, dpp_get<0xB1, 0xf>(am));       // quad_perm [1,0,3,2]
+    am = fmaxf(am, dpp_get<0x4E, 0xf>(am));       // quad_perm [2,3,0,1]: the block's amax in all four lanes
+    const int x = mx_exp(am);
+    const float s = mx_inv(x);
+    uint2 o;
+    o.x = pack_e4m3(a[0] * s, a[1] * s, a[2] * s, a[3] * s);
+    o.y = pack_e4m3(b[0] * s, b[1] * s, b[2] * s, b[3] * s);
+    reinterpret_cast<uint2*>(dst)[i] = o;
+    if ((i & 3) == 0) sc[i >> 2] = (uint8_t)(x + 127);
+  }
+}
+
+// e4m3 weight shadow -> its transpose: dst[dst_off + c * R + r] = src[src_off + r * C + c] for every matrix of the table (rows of four int64:
+// src_off, dst_off, R, C; offsets, R and C multiples of 8 -- a row that is not is skipped).  64 x 64-byte tiles through LDS: 8-byte loads
+// along the source rows, 8-byte stores along the destination rows.  grid (workgroups per matrix, matrices)
+__global__ __launch_bounds__(TPB) void k_fp8_transpose_shadow(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                              const int64_t* __restrict__ tab) {
+  __shared__ uint8_t tile[64][64 + 8];
+  const int64_t* t = tab + 4 * blockIdx.y;
+  const int64_t so = t[0], dof = t[1], R = t[2], C = t[3];
+  if (((so | dof | R | C) & 7) != 0 || R <= 0 || C <= 0) return;            // workgroup-uniform
+  const int64_t tr = (R + 63) >> 6, tc = (C + 63) >> 6;
+  for (int64_t tile_i = blockIdx.x; tile_i < tr * tc; tile_i += gridDim.x) {
+    const int64_t r0 = (tile_i / tc) * 64, c0 = (tile_i % tc) * 64;
+    __syncthreads();                                                         // the previous tile's readers are done
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int idx = threadIdx.x + TPB * j, rr = idx >> 3, ch = (idx & 7) * 8;
+      uint2 v = make_uint2(0u, 0u);
+      if (r0 + rr < R && c0 + ch < C) v = *reinterpret_cast<const uint2*>(src + so + (r0 + rr) * C + c0 + ch);
+      *reinterpret_cast<uint2*>(&tile[rr][ch]) = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int idx = threadIdx.x + TPB * j, cc = idx >> 3, rc = (idx & 7) * 8;
+      if (c0 + cc < C && r0 + rc < R) {
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          lo |= (uint32_t)tile[rc + k][cc] << (8 * k);
+          hi |= (uint32_t)tile[rc + 4 + k][cc] << (8 * k);
+        }
+        *reinterpret_cast<uint2*>(dst + dof + (c0 + cc) * R + r0 + rc) = make_uint2(lo, hi);
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------- LayerNorm + modulate with the e4m3 copy (norm.hip's k_ln_mod_fwd + one store)
@@ -205,8 +282,13 @@ struct Gemm8Args {
   const float* gate; int ldgate; int T;
   unsigned int* act_amax;                 // the caller's activation-range words (site 2 is raised by EPI_GELU's e4m3 output), or null
   int aux_q;                              // EPI_GELU: aux = GELU'(pre-activation) as one byte per element (common.h geluq_pack4), uint8 [M][ldaux]
+                                          // E8_DG_GELU: aux holds those codes (aux_q = 1) or the bf16 pre-activation
+  const uint8_t* a_sc;                    // E8_DG_*: A's E8M0 scales [M][K / 32] (MX dY)
+  uint8_t* c8_sc;                         // E8_DG_GELU: the MX copy of Cb goes to C8 [M][N] + c8_sc [M][N / 32]
+  float* colpart;                         // E8_DG_GELU: [M / 256][N] column sums of each tile row's result (fp32), or null
 };
-enum { E8_BF16 = 0, E8_GELU = 2, E8_GATE_RES = 3 };
+// E8_DG_BF16 / E8_DG_GELU: the dgrad form -- A = MX e4m3 dY with one scale byte per lane and 32-block, B = the transposed weight shadow
+enum { E8_BF16 = 0, E8_GELU = 2, E8_GATE_RES = 3, E8_DG_BF16 = 4, E8_DG_GELU = 5 };
 
 constexpr int FBM = 256, BKB = 128, NW = 8, NSLOT8 = 3;
 constexpr int A_BYTES = FBM * BKB, NA = FBM * 8 / 64 / NW;
@@ -221,6 +303,10 @@ template <int NTL> struct Tile8 {
 };
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// one dword per lane (LDS: lane * 4 from dst)
+__device__ __forceinline__ void dma4b(__amdgpu_buffer_rsrc_t rsrc, uint8_t* dst, int voff, int soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr8_t*)dst, 4, voff, soff, 0, 0);
+}
 __device__ __forceinline__ void dma16b(__amdgpu_buffer_rsrc_t rsrc, uint8_t* dst, int voff, int soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr8_t*)dst, 16, voff, soff, 0, 0);
 }
@@ -228,6 +314,15 @@ __device__ __forceinline__ void dma16b(__amdgpu_buffer_rsrc_t rsrc, uint8_t* dst
 __device__ __forceinline__ i32x8 frag32(const uint8_t* img, int row, int g) {
   const i32x4 lo = *reinterpret_cast<const i32x4*>(img + row * 128 + (((2 * g) ^ (row & 7)) << 4));
   const i32x4 hi = *reinterpret_cast<const i32x4*>(img + row * 128 + (((2 * g + 1) ^ (row & 7)) << 4));
+  return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+// The 16x16x128 f8 MFMA takes lane group g's 32 bytes as k = 16 g .. 16 g + 15 (first four registers) and 64 + 16 g .. 64 + 16 g + 15 (last
+// four), and its per-lane scale of group j covers k = 32 j .. 32 j + 31 (measured: tests/test_gpu_fp8_backward.py lane-map test).  frag32's
+// chunks 2g, 2g + 1 are a consistent K permutation -- harmless with unit scales -- but would put two 32-blocks under one scale; the MX form
+// loads chunks g and g + 4 so that the matrix core's k IS the memory k and group j's scale byte is that of the row's 32-block j.
+__device__ __forceinline__ i32x8 frag32_mx(const uint8_t* img, int row, int g) {
+  const i32x4 lo = *reinterpret_cast<const i32x4*>(img + row * 128 + ((g ^ (row & 7)) << 4));
+  const i32x4 hi = *reinterpret_cast<const i32x4*>(img + row * 128 + (((g + 4) ^ (row & 7)) << 4));
   return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
@@ -240,9 +335,14 @@ __device__ __forceinline__ i32x8 frag32(const uint8_t* img, int row, int g) {
 template <int EPI, int NTL, int NL = 0>
 __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
   using TL = Tile8<NTL>;
-  constexpr int FBN = TL::FBN, SLOT = TL::SLOT, NT8 = NTL;
+  // dgrad form: a slot also holds the A tile's scale bytes, [256 rows][4 32-blocks], sent by waves 0..3 (one dword per lane and row); waves
+  // 4..7 send theirs through the zero-length descriptor to the dummy kilobyte, so every wave issues NDMA8 pieces per k-step
+  constexpr bool MX = EPI == E8_DG_BF16 || EPI == E8_DG_GELU;
+  static_assert(!MX || NL == 0, "dgrad form: shared-wave tiles only");
+  static_assert(EPI != E8_DG_GELU || NTL == 8, "MX output: 32-blocks must not straddle tiles");
+  constexpr int FBN = TL::FBN, SLOT = TL::SLOT + (MX ? 1024 : 0), NT8 = NTL;
   constexpr int NWD = NL > 0 ? NL : NW;                                  // waves that issue LDS-DMA
-  constexpr int NA_ = FBM * 8 / 64 / NWD, NB = (TL::NB_TOTAL + NWD - 1) / NWD, NDMA8 = NA_ + NB;
+  constexpr int NA_ = FBM * 8 / 64 / NWD, NB = (TL::NB_TOTAL + NWD - 1) / NWD, NDMA8 = NA_ + NB + (MX ? 1 : 0);
   constexpr bool EVEN_ = TL::NB_TOTAL % NWD == 0;
   constexpr size_t DUMMY_AT = (size_t)NSLOT8 * SLOT;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
@@ -259,6 +359,8 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, g.M * K, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, g.N * K, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsNull = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, 0, 0x00020000);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsS =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(MX ? g.a_sc : g.B), 0, MX ? g.M * (K >> 5) : 0, 0x00020000);
   uint8_t* const dummy = smem8 + DUMMY_AT;
   const int lc16 = ((lane & 7) ^ ((lane >> 3) & 7)) << 4;
   const int dwave = NL > 0 ? wave - NW : wave;                       // (consumers of the loader form never use their plan)
@@ -267,6 +369,7 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
   for (int i = 0; i < NA_; ++i) a_off[i] = (m0 + (dwave + i * NWD) * 8 + (lane >> 3)) * K + lc16;
 #pragma unroll
   for (int i = 0; i < NB; ++i) b_off[i] = (n0 + (dwave + i * NWD) * 8 + (lane >> 3)) * K + lc16;
+  [[maybe_unused]] const int s_off = (m0 + (dwave & 3) * 64 + lane) * (K >> 5);
   auto issue = [&](int slot, int k0) {
     uint8_t* iA = smem8 + slot * SLOT;
     uint8_t* iB = iA + A_BYTES;
@@ -279,6 +382,10 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
         const bool ok = dwave + i * NWD < TL::NB_TOTAL;             // wave-uniform
         dma16b(ok ? rsB : rsNull, ok ? iB + (dwave + i * NWD) * 1024 : dummy, b_off[i], k0);
       }
+    }
+    if constexpr (MX) {
+      if (dwave < 4) dma4b(rsS, iB + TL::B_BYTES + dwave * 256, s_off, k0 >> 5);     // wave-uniform
+      else dma4b(rsNull, dummy, 0, 0);
     }
   };
   if constexpr (NL > 0) {
@@ -308,7 +415,7 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
     for (int nt = 0; nt < NT8; ++nt)
       bias_v[nt] = g.bias ? *reinterpret_cast<const float4*>(g.bias + n0 + nt * 16 + 4 * fg) : make_float4(0.f, 0.f, 0.f, 0.f);
   };
-  if constexpr (NL == 0) load_bias();
+  if constexpr (NL == 0 && !MX) load_bias();
   const float deq = 1.0f / (g.a_scale * *g.w_scale);
   if constexpr (NL == 0) {
     if (nk > 0) issue(0, 0);
@@ -321,6 +428,18 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
     if constexpr (NL == 0) { if (kt + 2 < nk) issue(slot >= 1 ? slot - 1 : 2, (kt + 2) * BKB); }
     const uint8_t* iA = smem8 + slot * SLOT;
     const uint8_t* iB = iA + A_BYTES;
+    if constexpr (MX) {
+      // this lane's scale operand: the E8M0 byte of 32-block fg of rows wave * 32 + fr (+ 16)
+      const i32x8 fa0 = frag32_mx(iA, wave * 32 + fr, fg), fa1 = frag32_mx(iA, wave * 32 + 16 + fr, fg);
+      const uint8_t* iS = iB + TL::B_BYTES;
+      const int sa0 = iS[(wave * 32 + fr) * 4 + fg], sa1 = iS[(wave * 32 + 16 + fr) * 4 + fg];
+#pragma unroll
+      for (int nt = 0; nt < NT8; ++nt) {
+        const i32x8 fb = frag32_mx(iB, nt * 16 + fr, fg);
+        acc[0][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa0, acc[0][nt], 0, 0, 0, 127, 0, sa0);
+        acc[1][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa1, acc[1][nt], 0, 0, 0, 127, 0, sa1);
+      }
+    } else {
     const i32x8 fa0 = frag32(iA, wave * 32 + fr, fg), fa1 = frag32(iA, wave * 32 + 16 + fr, fg);
 #pragma unroll
     for (int nt = 0; nt < NT8; ++nt) {
@@ -329,11 +448,89 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
       acc[0][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa0, acc[0][nt], 0, 0, 0, 127, 0, 127);
       acc[1][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa1, acc[1][nt], 0, 0, 0, 127, 0, 127);
     }
+    }
     slot = slot == 2 ? 0 : slot + 1;
   }
   constexpr bool BIAS_BY_HALF = NL > 0 && EPI == E8_GATE_RES;       // (that epilogue also holds gate + residual words: bias with them, half a row at a time)
   if constexpr (NL > 0 && !BIAS_BY_HALF) load_bias();
   // lane holds C[m0 + 32 wave + 16 mt + fr][n0 + 16 nt + 4 fg .. +3]
+  if constexpr (EPI == E8_DG_GELU) {
+    // fc2 dgrad * GELU' (as csrc/gemm.hip EPI_DGELU / EPI_DGELUQ): d_hpre in bf16, its MX e4m3 copy quantised from the bf16-ROUNDED values
+    // (= sfron_cast_mx8 of the bf16 output, bit for bit), and the column sums of the fp32 values per tile row (fc1.bias gradient partials).
+    // A 32-block of a row = tiles 2 np, 2 np + 1 of the four lanes fg that hold that row.
+    const int colp = n0 + pair_col(fg);
+    f32x4 cs[NT8];
+#pragma unroll
+    for (int nt = 0; nt < NT8; ++nt) cs[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int row = m0 + wave * 32 + mt * 16 + fr;
+      f32x4 gp[NT8];
+      if (g.aux_q) {                                                          // kernel-uniform
+        const uint8_t* const aq = reinterpret_cast<const uint8_t*>(g.aux) + (size_t)row * g.ldaux;
+#pragma unroll
+        for (int np = 0; np < NT8 / 2; ++np) {
+          unsigned a, b;
+          pair_unpack8(*reinterpret_cast<const uint2*>(aq + colp + np * 32), a, b);
+          gp[2 * np] = geluq_unpack4(a); gp[2 * np + 1] = geluq_unpack4(b);
+        }
+      } else {
+        const __bf16* const ap = g.aux + (size_t)row * g.ldaux + n0 + 4 * fg;
+#pragma unroll
+        for (int nt = 0; nt < NT8; ++nt) gp[nt] = gelu_tanh_grad4(bf2f4(*reinterpret_cast<const bf16x4*>(ap + nt * 16)));
+      }
+      bf16x4 ob[NT8];
+      unsigned c8[NT8];
+      unsigned scw = 0;
+#pragma unroll
+      for (int nt = 0; nt < NT8; ++nt) {
+        const f32x4 r = (acc[mt][nt] * deq) * gp[nt];
+        cs[nt] += r;
+        ob[nt] = f2bf4(r);
+      }
+#pragma unroll
+      for (int np = 0; np < NT8 / 2; ++np) {
+        const f32x4 h0 = bf2f4(ob[2 * np]), h1 = bf2f4(ob[2 * np + 1]);
+        float am = fmaxf(amax4v(h0), amax4v(h1));
+        am = fmaxf(am, __shfl_xor(am, 16, 64));
+        am = fmaxf(am, __shfl_xor(am, 32, 64));
+        const int x = mx_exp(am);
+        const float s = mx_inv(x);
+        c8[2 * np] = pack_e4m3(h0[0] * s, h0[1] * s, h0[2] * s, h0[3] * s);
+        c8[2 * np + 1] = pack_e4m3(h1[0] * s, h1[1] * s, h1[2] * s, h1[3] * s);
+        scw |= (unsigned)(x + 127) << (8 * np);
+      }
+      __bf16* const r = g.Cb + (size_t)row * g.ldcb;
+#pragma unroll
+      for (int np = 0; np < NT8 / 2; ++np) *reinterpret_cast<uint4*>(r + colp + np * 32) = pair_pack(ob[2 * np], ob[2 * np + 1]);
+      uint8_t* const r8 = g.C8 + (size_t)row * g.N;
+#pragma unroll
+      for (int np = 0; np < NT8 / 2; ++np) *reinterpret_cast<uint2*>(r8 + colp + np * 32) = pair_pack8(c8[2 * np], c8[2 * np + 1]);
+      if (fg == 0) *reinterpret_cast<uint32_t*>(g.c8_sc + (size_t)row * (g.N >> 5) + (n0 >> 5)) = scw;
+    }
+    if (g.colpart) {                                                          // kernel-uniform
+      // the 16 lanes that share fg hold the same 4 columns: row16_sum, then the 8 waves meet in LDS (free: every wave is past the main
+      // loop after the barrier) and are added in wave order
+#pragma unroll
+      for (int nt = 0; nt < NT8; ++nt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cs[nt][j] = row16_sum(cs[nt][j]);
+      __syncthreads();
+      float* red = reinterpret_cast<float*>(smem8);                         // [NW][FBN]
+      if (fr == 0) {
+#pragma unroll
+        for (int nt = 0; nt < NT8; ++nt) *reinterpret_cast<f32x4*>(red + wave * FBN + nt * 16 + 4 * fg) = cs[nt];
+      }
+      __syncthreads();
+      for (int c = tid; c < FBN; c += NW * 64) {
+        float x = red[c];
+#pragma unroll
+        for (int w2 = 1; w2 < NW; ++w2) x += red[w2 * FBN + c];
+        g.colpart[(size_t)tm * g.N + n0 + c] = x;
+      }
+    }
+    return;
+  }
   [[maybe_unused]] float act_am = 0.f;          // E8_GELU: max |gelu * c8_scale| of this thread's values (g_act_amax site 2)
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) {
@@ -363,11 +560,13 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
       }
       const int col = n0 + nt * 16 + 4 * fg;
       f32x4 v = acc[mt][nt] * deq;
-      const float4 bv = bias_v[BIAS_BY_HALF ? nt % NH : nt];
-      v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
+      if constexpr (!MX) {
+        const float4 bv = bias_v[BIAS_BY_HALF ? nt % NH : nt];
+        v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
+      }
       // bf16 / e4m3 results are kept per tile and leave in PAIRS of tiles after the loop (common.h pair_pack: 16-byte bf16 pieces, 8-byte
       // e4m3 pieces; the store tail is issue-bound)
-      if constexpr (EPI == E8_BF16) {
+      if constexpr (EPI == E8_BF16 || EPI == E8_DG_BF16) {
         ob[nt] = bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
       } else if constexpr (EPI == E8_GELU) {
         float h0, h1, h2, h3;
@@ -403,7 +602,7 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_gemm8(Gemm8Args g) {
         for (int nt = 0; nt < NT8; ++nt) *reinterpret_cast<bf16x4*>(r + n0 + nt * 16 + 4 * fg) = t[nt];
       }
     };
-    if constexpr (EPI == E8_BF16 || EPI == E8_GELU) put(g.Cb, g.ldcb, ob);
+    if constexpr (EPI == E8_BF16 || EPI == E8_GELU || EPI == E8_DG_BF16) put(g.Cb, g.ldcb, ob);
     if constexpr (EPI == E8_GATE_RES) put(g.aux, g.ldaux, ab);
     if constexpr (EPI == E8_GELU) {
       if (g.aux_q) {
@@ -438,6 +637,9 @@ template __global__ void k_gemm8<E8_GATE_RES, 8, 4>(Gemm8Args);
 template __global__ void k_gemm8<E8_BF16, 9, 4>(Gemm8Args);
 template __global__ void k_gemm8<E8_GELU, 9, 4>(Gemm8Args);
 template __global__ void k_gemm8<E8_GATE_RES, 9, 4>(Gemm8Args);
+template __global__ void k_gemm8<E8_DG_BF16, 8>(Gemm8Args);
+template __global__ void k_gemm8<E8_DG_BF16, 9>(Gemm8Args);
+template __global__ void k_gemm8<E8_DG_GELU, 8>(Gemm8Args);
 
 int g_fp8_loader_waves = 0;     // process-wide form of the fp8 tiles: 4 = loader waves (sfron_gemm_loader_waves(9)); measured in the config-5 step:
                                 // 65.2 / 64.0 / 64.8 ms against 63.5 / 64.1 / 64.1 for the shared-wave form -- off
@@ -445,7 +647,8 @@ int g_fp8_loader_waves = 0;     // process-wide form of the fp8 tiles: 4 = loade
 namespace {
 template <int EPI, int NTL, int NL>
 int launch8t(const Gemm8Args& g, hipStream_t s) {
-  const size_t lds = (size_t)NSLOT8 * Tile8<NTL>::SLOT + 1024;      // (+ the dummy kilobyte of uneven DMA plans)
+  constexpr bool MX = EPI == E8_DG_BF16 || EPI == E8_DG_GELU;
+  const size_t lds = (size_t)NSLOT8 * (Tile8<NTL>::SLOT + (MX ? 1024 : 0)) + 1024;      // (+ the dummy kilobyte of uneven DMA plans)
   static std::atomic<uint64_t> done{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -509,6 +712,51 @@ int sfron_fp8_gemm(const sfron_fp8_gemm_desc* d, void* stream) {
     default:
       return SFRON_ERR_UNSUPPORTED;
   }
+}
+
+int sfron_fp8_dgrad(const sfron_fp8_dgrad_desc* d, void* stream) {
+  SFRON_CHECK_ARG(d && d->A && d->a_scales && d->B && d->w_scale && d->c_bf16);
+  if (!sfron_fp8_gemm_supported(d->M, d->N, d->K)) return SFRON_ERR_UNSUPPORTED;
+  SFRON_CHECK_ARG((long)d->M * d->K < (1L << 31) && (long)d->N * d->K < (1L << 31));        // 32-bit buffer offsets
+  SFRON_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->B) & 15) == 0 && ((uintptr_t)d->a_scales & 3) == 0);
+  SFRON_CHECK_ARG(d->tile_hint == 0 || d->tile_hint == 8 || d->tile_hint == 9);
+  Gemm8Args g{};
+  g.A = d->A; g.B = d->B; g.M = d->M; g.N = d->N; g.K = d->K; g.w_scale = d->w_scale; g.a_scale = 1.0f; g.a_sc = d->a_scales;
+  g.Cb = (__bf16*)d->c_bf16; g.ldcb = d->ldc_bf16;
+  hipStream_t s = (hipStream_t)stream;
+  if (d->epilogue == SFRON_EPI_BF16) {
+    SFRON_CHECK_ARG(g.ldcb % 4 == 0 && g.ldcb >= g.N);
+    const int ntl = d->tile_hint ? d->tile_hint : pick_ntl(g.M, g.N);
+    if (g.N % (ntl * 16)) return SFRON_ERR_UNSUPPORTED;
+    return ntl == 9 ? launch8t<E8_DG_BF16, 9, 0>(g, s) : launch8t<E8_DG_BF16, 8, 0>(g, s);
+  }
+  if (d->epilogue == SFRON_EPI_DGELU || d->epilogue == SFRON_EPI_DGELU_Q) {
+    // 256 x 128 tiles only: a 32-block of the MX output must not straddle two tiles
+    if (g.N % 128 || d->tile_hint == 9) return SFRON_ERR_UNSUPPORTED;
+    SFRON_CHECK_ARG(d->aux && d->c_e4m3 && d->c_scales && g.ldcb % 8 == 0 && g.ldcb >= g.N && d->ldaux >= g.N);
+    SFRON_CHECK_ARG(((uintptr_t)d->c_bf16 & 15) == 0 && ((uintptr_t)d->c_e4m3 & 7) == 0 && ((uintptr_t)d->c_scales & 3) == 0);
+    g.aux_q = d->epilogue == SFRON_EPI_DGELU_Q;
+    if (g.aux_q) SFRON_CHECK_ARG(d->ldaux % 8 == 0 && ((uintptr_t)d->aux & 7) == 0);
+    else SFRON_CHECK_ARG(d->ldaux % 4 == 0 && ((uintptr_t)d->aux & 7) == 0);
+    g.aux = (__bf16*)d->aux; g.ldaux = d->ldaux; g.C8 = d->c_e4m3; g.c8_sc = d->c_scales; g.colpart = d->col_partials;
+    return launch8t<E8_DG_GELU, 8, 0>(g, s);
+  }
+  return SFRON_ERR_UNSUPPORTED;
+}
+
+int sfron_cast_mx8(const uint16_t* src, int M, int N, uint8_t* dst, uint8_t* scales, void* stream) {
+  SFRON_CHECK_ARG(src && dst && scales && M > 0 && N > 0 && N % 32 == 0 && (((uintptr_t)src) & 15) == 0 && ((uintptr_t)dst & 7) == 0);
+  const int64_t n = (int64_t)M * N;
+  hipLaunchKernelGGL(k_cast_mx8, dim3(grid_for(n >> 3)), dim3(TPB), 0, (hipStream_t)stream, (const __bf16*)src, n, dst, scales);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_fp8_transpose_shadow(const uint8_t* w8, uint8_t* w8t, const int64_t* table, int n_matrices, void* stream) {
+  SFRON_CHECK_ARG(w8 && w8t && table && n_matrices > 0 && n_matrices <= 65535 && (((uintptr_t)w8 | (uintptr_t)w8t) & 7) == 0);
+  hipLaunchKernelGGL(k_fp8_transpose_shadow, dim3(256, n_matrices), dim3(TPB), 0, (hipStream_t)stream, w8, w8t, table);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
 }
 
 int sfron_fp8_quant_tensors(const float* params, const int64_t* table, int n_tensors, const float* scales, uint32_t* amax_bits,

@@ -142,11 +142,16 @@ class DitEngine:
     # ------------------------------------------------------------------ config 5: fp8 (e4m3) forward GEMMs
     FP8_ACT_SCALES = (8.0, 32.0, 16.0)     # LayerNorm+modulate output, attention output, gelu(fc1): static powers of two
 
-    def enable_fp8(self, act_scales=None):
+    def enable_fp8(self, act_scales=None, backward=False):
         """Run the four token GEMMs of every block's FORWARD pass on the fp8 matrix core (BASELINE config 5): an e4m3 shadow of
         the block weights with one power-of-two scale per tensor (re-quantised after every optimizer step: fp8_requantize), e4m3
-        activations written by their producers.  The backward pass keeps bf16 operands (straight-through estimator)."""
+        activations written by their producers.  The backward pass keeps bf16 operands (straight-through estimator) unless
+        ``backward=True``: then its four dgrads per block run on the fp8 matrix core too (enable_fp8_backward)."""
         L = _lib.lib()
+        if backward:
+            self._check_fp8_dgrad_shapes()
+        else:
+            self.disable_fp8_backward()               # a re-enable without the backward must not leave the handle armed on the old shadow
         c, lay = self.cfg, self.layout
         M = c.batch * self.tokens
         D, F = c.hidden, c.mlp_hidden
@@ -177,7 +182,68 @@ class DitEngine:
             act_amax=torch.zeros(3, dtype=torch.int32, device=self.device),
             ws=torch.empty(ws, dtype=torch.uint8, device=self.device))
         self.fp8_requantize(fresh=True)
+        if backward:
+            self.enable_fp8_backward()
         return self
+
+    def _check_fp8_dgrad_shapes(self):
+        L, c = _lib.lib(), self.cfg
+        M, D, F = c.batch * self.tokens, c.hidden, c.mlp_hidden
+        for N, K in ((D, 3 * D), (D, D), (F, D), (D, F)):          # dX[M][in] = dY[M][out] W[out][in]: (M, in, out)
+            if not L.sfron_fp8_gemm_supported(M, N, K) or F % 128:
+                raise _lib.SfronError(f"fp8 backward: dgrad {M}x{N}x{K} is not a multiple of the 256x128x128 fp8 tile")
+
+    def enable_fp8_backward(self, w8t=None):
+        """The four dgrads of every block on the fp8 matrix core (sfron_aux_set_fp8_dgrad): dY cast to MX e4m3 (one E8M0 scale per 32
+        elements of a row) times a TRANSPOSED copy of the e4m3 weight shadow, re-derived from the shadow in front of every backward
+        pass (fp8_transpose).  Needs enable_fp8() first.  w8t: another engine's transposed shadow over the same parameters (sibling())."""
+        if self.fp8 is None:
+            raise _lib.SfronError("fp8 backward needs the fp8 forward (enable_fp8) first")
+        self._check_fp8_dgrad_shapes()
+        L, c, lay, f = _lib.lib(), self.cfg, self.layout, self.fp8
+        if w8t is None:
+            D, F = c.hidden, c.mlp_hidden
+            base = lay["blocks"] & ~255                # the transposed matrices sit at their arena offsets minus this (16-byte aligned)
+            rows = []
+            for l in range(c.depth):
+                b = lay["blocks"] + l * lay["blk_stride"]
+                for key, R, C in (("qkv_w", 3 * D, D), ("proj_w", D, D), ("fc1_w", F, D), ("fc2_w", D, F)):
+                    rows.append((b + lay[key], b + lay[key] - base, R, C))
+            # the transpose kernel takes 8-byte pieces (and skips a table row that does not allow them): refuse such a layout here, where it
+            # can be reported, instead of leaving a zero-filled matrix behind
+            bad = [r for r in rows if any(v % 8 for v in r)]
+            if bad:
+                raise _lib.SfronError(f"fp8 backward: block matrix offsets / dimensions must be multiples of 8 (got {bad[0]})")
+            w8t = dict(t=torch.zeros(lay["blocks"] + c.depth * lay["blk_stride"] - base, dtype=torch.uint8, device=self.device),
+                       table=torch.tensor(rows, dtype=torch.int64, device=self.device), n=len(rows))
+        f["w8t"] = w8t
+        # this engine's own MX operands (a sibling's chain runs at the same time on another stream)
+        f["mx"] = torch.empty(L.sfron_dit_fp8_dgrad_workspace_bytes(ctypes.byref(c)), dtype=torch.uint8, device=self.device)
+        check(L.sfron_aux_set_fp8_dgrad(self.aux, ptr(w8t["t"]), ptr(f["scales"]), ptr(f["mx"])), "aux_set_fp8_dgrad")
+        self.fp8_transpose()
+        return self
+
+    def disable_fp8_backward(self):
+        """Back to bf16 dgrads (the fp8 forward, if enabled, stays): disarms the aux handle and drops this engine's transposed shadow and MX
+        operands.  No-op when the fp8 backward is not enabled."""
+        if self.aux is not None:
+            check(_lib.lib().sfron_aux_set_fp8_dgrad(self.aux, None, None, None), "aux_set_fp8_dgrad(disarm)")
+        if self.fp8 is not None:
+            self.fp8.pop("w8t", None)
+            self.fp8.pop("mx", None)
+
+    def fp8_transpose(self):
+        """Transposed e4m3 shadow <- the current shadow (one launch over every block matrix, on the current stream).  Every backward pass
+        of an engine with the fp8 dgrads runs it first, behind any optimizer sweep still in flight (drain_sweep): whoever wrote the shadow
+        last -- fp8_requantize, a re-quantising sweep, a block sweep left beside the next forward pass -- the dgrads read its transpose."""
+        f = self.fp8
+        check(_lib.lib().sfron_fp8_transpose_shadow(ptr(f["w8"]), ptr(f["w8t"]["t"]), ptr(f["w8t"]["table"]), f["w8t"]["n"], stream_ptr()),
+              "fp8_transpose_shadow")
+
+    def _before_backward(self):
+        if self.fp8 is not None and self.fp8.get("w8t") is not None:
+            self.drain_sweep()
+            self.fp8_transpose()
 
     def fp8_activation_range(self, reset=True):
         """How much of the e4m3 range the activations used since the last reset (the activation scales are static and the conversion
@@ -218,6 +284,8 @@ class DitEngine:
         if getattr(other, "fp8", None) is not None:
             ws = _lib.lib().sfron_dit_fp8_workspace_bytes(ctypes.byref(self.cfg))
             self.fp8 = dict(other.fp8, ws=torch.empty(ws, dtype=torch.uint8, device=self.device))
+            if other.fp8.get("w8t") is not None:
+                self.enable_fp8_backward(w8t=other.fp8["w8t"])
 
     # ------------------------------------------------------------------ passes
     def block_sweep_setup(self):
@@ -346,6 +414,7 @@ class DitEngine:
     def backward_dp(self, d_out, y, drop=None):
         """Backward pass that records per-block completion events and parks proj.bias / fc2.bias gradients in ``late_bias``."""
         self.dp_setup()
+        self._before_backward()
         check(_lib.lib().sfron_dit_backward_dp(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out), ptr(y),
                                                ptr(drop), ptr(self.workspace), ptr(self.grads), self.aux, self._dp_handles,
                                                ptr(self.late_bias), ptr(self.ada_dmod), ptr(self.ada_sc), stream_ptr()), "dit_backward_dp")
@@ -360,6 +429,7 @@ class DitEngine:
             self._ada_f = (torch.empty(self.cfg.batch, NM, dtype=torch.bfloat16, device=self.device),
                            torch.empty(self.cfg.batch, self.cfg.hidden, dtype=torch.bfloat16, device=self.device))
         dmod, sc = self._ada_f
+        self._before_backward()
         check(_lib.lib().sfron_dit_backward_dp(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out), ptr(y),
                                                ptr(drop), ptr(self.workspace), ptr(self.grads), self.aux, None, None, ptr(dmod), ptr(sc),
                                                stream_ptr()), "dit_backward (factored adaLN gradient)")
@@ -437,6 +507,7 @@ class DitEngine:
 
     def backward(self, d_out, y, drop=None, grads=None):
         g = self.grads if grads is None else grads
+        self._before_backward()
         check(_lib.lib().sfron_dit_backward(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out),
                                             ptr(y), ptr(drop), ptr(self.workspace), ptr(g), self.aux, stream_ptr()), "dit_backward")
         return g
