@@ -340,6 +340,29 @@ typedef struct sfron_fp8_dgrad_desc {
 } sfron_fp8_dgrad_desc;
 int sfron_fp8_dgrad(const sfron_fp8_dgrad_desc* desc /* HOST pointer */, void* stream);
 
+/* fp8 WEIGHT GRADIENTS (opt-in, sfron_aux_set_fp8_wgrad): dW[N][K] = dY[M][N]^T . X[M][K] reduces over the M tokens, so BOTH operands are
+ * MX-scaled along the tokens -- the rule above applied to the transposed matrices: one E8M0 byte per 32 consecutive tokens of a column.
+ * bf16 src [M][W] -> MX e4m3 of src^T: dst [W][M] + scales [W][M / 32]; sfron_cast_mx8_t(x) == sfron_cast_mx8(x^T) bit for bit.
+ * M % 32 == 0, W % 8 == 0. */
+int sfron_cast_mx8_t(const uint16_t* src, int M, int W, uint8_t* dst, uint8_t* scales, void* stream);
+/* c_f32[N][K] (row stride ldc, fp32, overwritten) = (A[N][M] with its MX scales) . (B[K][M] with its MX scales)^T: A = sfron_cast_mx8_t(dY),
+ * B = sfron_cast_mx8_t(X); each operand's scale bytes go to the MFMA per lane.  192 x 192 output tiles (those of the bf16 weight-gradient
+ * GEMM): sumsq_partials / sumsq_mask as in sfron_gemm_desc -- fp64 [sfron_gemm_sumsq_partials(N, K, M)], partial t = sum over output tile t
+ * of (mask ? c : 0)^2, mask over the output (element (n, k) at n * ldc + k) or NULL.  sfron_fp8_wgrad_supported: N % 192 == K % 192 == 0,
+ * M % 128 == 0, N * M and K * M < 2^31. */
+typedef struct sfron_fp8_wgrad_desc {
+  const uint8_t* A;                  /* MX e4m3 dY^T [N][M] */
+  const uint8_t* a_scales;           /* its E8M0 bytes [N][M / 32] */
+  const uint8_t* B;                  /* MX e4m3 X^T [K][M] */
+  const uint8_t* b_scales;           /* its E8M0 bytes [K][M / 32] */
+  int N, K, M;
+  float* c_f32; int ldc;
+  const uint8_t* sumsq_mask;
+  double* sumsq_partials;
+} sfron_fp8_wgrad_desc;
+int sfron_fp8_wgrad_supported(int N, int K, int M);
+int sfron_fp8_wgrad(const sfron_fp8_wgrad_desc* desc /* HOST pointer */, void* stream);
+
 /* ------------------------------------------------------------------ convolutional U-Net blocks (conv.hip)
  * Replaces the Conv2d / GroupNorm / bmm-softmax sequences of DDPM/models/diffusion.py:43-192,283-413 (Conditional_Model) forward
  * and backward.  Activations are NHWC: a [batch * H * W][C] row-major matrix (bf16 where they feed a GEMM, fp32 elsewhere). */
@@ -790,6 +813,14 @@ int sfron_aux_streams(void* aux, void** side /* HOST out */, void** side2 /* HOS
  * do not take. */
 int64_t sfron_dit_fp8_dgrad_workspace_bytes(const sfron_dit_cfg* cfg);
 int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales, void* mx_workspace);
+/* Arms the handle for fp8 weight gradients: every sfron_dit_backward / _dp call through it then forms the qkv, proj, fc1 and fc2 weight
+ * gradients of each block with sfron_fp8_wgrad -- dY and the forward input X (xmod1 / o / xmod2 / h) cast by sfron_cast_mx8_t on the
+ * weight-gradient stream itself, into this handle's workspace (one operand pair per weight-gradient stream: reuse follows that stream's
+ * order).  Biases, adaLN, the embedders and the final layer are unchanged.  Independent of the fp8 forward and of the fp8 dgrads.
+ * workspace: sfron_dit_fp8_wgrad_workspace_bytes(cfg) bytes, 16-byte aligned; NULL disarms.  A backward pass on an armed handle returns
+ * SFRON_ERR_UNSUPPORTED for block shapes sfron_fp8_wgrad_supported refuses. */
+int64_t sfron_dit_fp8_wgrad_workspace_bytes(const sfron_dit_cfg* cfg);
+int sfron_aux_set_fp8_wgrad(void* aux, void* workspace);
 int sfron_aux_destroy(void* aux);
 
 #ifdef __cplusplus

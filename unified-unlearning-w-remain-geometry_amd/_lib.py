@@ -149,6 +149,19 @@ _PROTOS.update({
 })
 
 
+class Fp8WgradDesc(ctypes.Structure):
+    """Mirror of sfron_fp8_wgrad_desc."""
+    _fields_ = [("A", c_void_p), ("a_scales", c_void_p), ("B", c_void_p), ("b_scales", c_void_p), ("N", c_int), ("K", c_int), ("M", c_int),
+                ("c_f32", c_void_p), ("ldc", c_int), ("sumsq_mask", c_void_p), ("sumsq_partials", c_void_p)]
+
+
+_PROTOS.update({
+    "sfron_cast_mx8_t": (c_int, [_P, c_int, c_int, _P, _P, _S]),
+    "sfron_fp8_wgrad_supported": (c_int, [c_int, c_int, c_int]),
+    "sfron_fp8_wgrad": (c_int, [POINTER(Fp8WgradDesc), _S]),
+})
+
+
 class BGemmDesc(ctypes.Structure):
     """Mirror of sfron_bgemm_desc."""
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int), ("lda", c_int), ("ldb", c_int),
@@ -261,6 +274,8 @@ _PROTOS.update({
     "sfron_dit_fp8_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_dit_fp8_dgrad_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_aux_set_fp8_dgrad": (c_int, [c_void_p, _P, _P, _P]),
+    "sfron_dit_fp8_wgrad_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
+    "sfron_aux_set_fp8_wgrad": (c_int, [c_void_p, _P]),
     "sfron_dit_forward_fp8": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
     "sfron_probe_create": (c_int, [c_int, POINTER(c_void_p)]),
     "sfron_probe_reset": (c_int, [c_void_p]),

@@ -241,7 +241,8 @@ static int ablate_mask() {
 // depends on) run concurrently with the dgrad / elementwise chain and fill the CUs its tile counts leave idle
 struct Probe;
 struct Aux { hipStream_t side, side2; hipEvent_t produced[4], consumed[8], done, join2, ada_ready, ada_factors; Probe* probe; const uint8_t* sq_mask; double* sq_partials; int dev;
-             const uint8_t* w8t; const float* w8_scales; char* mx_ws; };      // fp8 dgrads (sfron_aux_set_fp8_dgrad), w8t NULL = off
+             const uint8_t* w8t; const float* w8_scales; char* mx_ws;       // fp8 dgrads (sfron_aux_set_fp8_dgrad), w8t NULL = off
+             char* wg_ws; };                                                 // fp8 weight gradients (sfron_aux_set_fp8_wgrad), NULL = off
 
 // The two weight-gradient streams of a handle come from a per-device FREE LIST and go back to it when the handle is destroyed: a process
 // that builds one engine after another (bench.py's configuration legs, set_batch_size(), a test session) keeps running on the SAME
@@ -300,6 +301,11 @@ int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales
   SFRON_CHECK_ARG(aux && (!w8t || (w_scales && mx_workspace)));
   Aux* a = (Aux*)aux;
   a->w8t = w8t; a->w8_scales = w8t ? w_scales : nullptr; a->mx_ws = w8t ? (char*)mx_workspace : nullptr;
+  return SFRON_OK;
+}
+int sfron_aux_set_fp8_wgrad(void* aux, void* workspace) {
+  SFRON_CHECK_ARG(aux && ((uintptr_t)workspace & 15) == 0);
+  ((Aux*)aux)->wg_ws = (char*)workspace;
   return SFRON_OK;
 }
 int sfron_aux_wait_ada(void* aux, void* stream) {
@@ -478,6 +484,28 @@ int64_t sfron_dit_fp8_dgrad_workspace_bytes(const sfron_dit_cfg* cfg) {
   Dims d;
   if (make_dims(cfg, d) != SFRON_OK) return -1;
   return (int64_t)mx_ws(d, nullptr, nullptr);
+}
+
+// fp8 weight gradients: the MX operand pair (dY^T, X^T: e4m3 [width][M] + E8M0 [width][M / 32] each) of the weight-gradient GEMM in flight on
+// each weight-gradient stream -- [0] side (qkv, fc1, fc2, and proj without the paired form: widest F or 3 D), [1] side2 (proj: D x D).  A
+// stream's casts of block l + 1 queue behind its own GEMM of block l, and the two streams never share a pair.
+struct WgOps { uint8_t *a, *a_sc, *b, *b_sc; };
+static size_t wg_ws(const Dims& d, char* base, WgOps* m) {
+  size_t o = 0;
+  auto take = [&](size_t bytes) { char* r = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return (uint8_t*)r; };
+  const size_t wide = (size_t)(d.F > 3 * d.D ? d.F : 3 * d.D);
+  const size_t wa[2] = {wide, (size_t)d.D}, wb[2] = {(size_t)(d.F > d.D ? d.F : d.D), (size_t)d.D};
+  for (int i = 0; i < 2; ++i) {
+    uint8_t* a = take((size_t)d.M * wa[i]); uint8_t* as = take((size_t)d.M * wa[i] / 32);
+    uint8_t* b = take((size_t)d.M * wb[i]); uint8_t* bs = take((size_t)d.M * wb[i] / 32);
+    if (m) { m[i].a = a; m[i].a_sc = as; m[i].b = b; m[i].b_sc = bs; }
+  }
+  return o;
+}
+int64_t sfron_dit_fp8_wgrad_workspace_bytes(const sfron_dit_cfg* cfg) {
+  Dims d;
+  if (make_dims(cfg, d) != SFRON_OK) return -1;
+  return (int64_t)wg_ws(d, nullptr, nullptr);
 }
 
 int64_t sfron_dit_fp8_workspace_bytes(const sfron_dit_cfg* cfg) {
@@ -705,6 +733,16 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
   // db (optional): the bias gradient sum_rows dY of the same Linear.  Where the three-slot weight-gradient kernel takes the
   // shape it comes out of that GEMM (row sums of dY^T against a ones fragment); otherwise a column-sum launch precedes it.
   bool probe_block = false;
+  // fp8 weight gradients (sfron_aux_set_fp8_wgrad): dY and X cast to MX e4m3 along the tokens on the weight-gradient stream, then
+  // sfron_fp8_wgrad -- the bias gradients keep reading the bf16 dY
+  const bool f8w = ax && ax->wg_ws;
+  WgOps wg[2] = {};
+  if (f8w) {
+    if (!sfron_fp8_wgrad_supported(3 * D, D, M) || !sfron_fp8_wgrad_supported(D, D, M) || !sfron_fp8_wgrad_supported(d.F, D, M) ||
+        !sfron_fp8_wgrad_supported(D, d.F, M))
+      return SFRON_ERR_UNSUPPORTED;
+    (void)wg_ws(d, ax->wg_ws, wg);
+  }
   auto wgrad_on = [&](void* side, const void* dY, const void* X, int N, int K, float* dW, float* db) -> int {
     sfron_gemm_desc q = wgrad_desc(dY, X, M, N, K, dW);
     if (db) {
@@ -713,10 +751,6 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
         q.rowsum_ws = ax ? w.csum2 : w.csum;            // [K / 192][N] partial rows (<= CSUM_PARTS rows of the widest output)
       } else RUN(sfron_colsum(dY, 1, M, N, N, ax ? w.csum2 : w.csum, CSUM_PARTS, db, side));
     }
-    // roofline probe: an event pair on the weight-gradient stream around the GEMM itself (all four weight gradients of the probed blocks)
-    Probe* pr = (ax && ax->probe && probe_block && ax->probe->used < ax->probe->cap) ? ax->probe : nullptr;
-    if (pr) (void)hipEventRecord(pr->ev[2 * pr->used], (hipStream_t)side);
-    struct Close { Probe* p; void* s; ~Close() { if (p) { (void)hipEventRecord(p->ev[2 * p->used + 1], (hipStream_t)s); p->used++; } } } close{pr, side};
     // measured: the splits shorten the side stream (proj 175 -> 60 us) but the backward pass is bound by total CU time, and
     // the slab traffic + reductions make the step 0.5-2 ms SLOWER -> off unless SFRON_ABLATE bit 1 asks for the A-B run
     const int sp = (ablate_mask() & 2) ? wgrad_splits(N, K, M) : 1;
@@ -727,6 +761,22 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
       q.sumsq_mask = sq_mask ? sq_mask + (dW - grads) : nullptr;
     } else if (sq_next) return SFRON_ERR_UNSUPPORTED;       // (debug-knob builds only: an ablation that changes the weight-gradient form)
     sq_next = nullptr;
+    const WgOps& op = wg[ax && side == (void*)ax->side2 ? 1 : 0];
+    if (f8w) {
+      if (sp > 1 || q.tile_hint || q.a_rowsum) return SFRON_ERR_UNSUPPORTED;      // (debug-knob builds only, as above)
+      RUN(sfron_cast_mx8_t((const uint16_t*)dY, M, N, op.a, op.a_sc, side));
+      RUN(sfron_cast_mx8_t((const uint16_t*)X, M, K, op.b, op.b_sc, side));
+    }
+    // roofline probe: an event pair on the weight-gradient stream around the GEMM itself (all four weight gradients of the probed blocks)
+    Probe* pr = (ax && ax->probe && probe_block && ax->probe->used < ax->probe->cap) ? ax->probe : nullptr;
+    if (pr) (void)hipEventRecord(pr->ev[2 * pr->used], (hipStream_t)side);
+    struct Close { Probe* p; void* s; ~Close() { if (p) { (void)hipEventRecord(p->ev[2 * p->used + 1], (hipStream_t)s); p->used++; } } } close{pr, side};
+    if (f8w) {
+      sfron_fp8_wgrad_desc f{};
+      f.A = op.a; f.a_scales = op.a_sc; f.B = op.b; f.b_scales = op.b_sc; f.N = N; f.K = K; f.M = M; f.c_f32 = dW; f.ldc = K;
+      f.sumsq_mask = q.sumsq_mask; f.sumsq_partials = q.sumsq_partials;
+      return sfron_fp8_wgrad(&f, side);
+    }
     RUN(sfron_gemm_bf16(&q, side));
     if (sp > 1) RUN(sfron_reduce_chunks(w.wslab, 1, sp, N * K, dW, N * K, 0, side));
     return SFRON_OK;

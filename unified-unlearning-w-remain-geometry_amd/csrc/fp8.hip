@@ -12,7 +12,9 @@
 // The backward pass keeps bf16 operands (the quantisation is a straight-through estimator, as in oracle/fp8_ref.py) unless the caller arms
 // the fp8 dgrads (sfron_aux_set_fp8_dgrad): the four input-gradient products of a block then multiply an MX-scaled e4m3 dY (one E8M0 scale
 // per 32 consecutive elements of a row, sfron_cast_mx8) by a TRANSPOSED copy of the e4m3 weight shadow (sfron_fp8_transpose_shadow) on the
-// same scaled MFMA, the dY scales fed per lane.  e4m3 = OCP e4m3fn (gfx950's v_cvt_pk_fp8_f32), round to nearest even, saturating at +-448.
+// same scaled MFMA, the dY scales fed per lane.  The fp8 weight gradients (sfron_aux_set_fp8_wgrad, independent of both) take dY and X MX-scaled
+// along the TOKENS (k_mx8_cast_t) and multiply them on the 192 x 192 tile of k_wgrad8, both scales fed per lane.
+// e4m3 = OCP e4m3fn (gfx950's v_cvt_pk_fp8_f32), round to nearest even, saturating at +-448.
 //
 // GEMM kernel: C[M][N] = deq * (A8[M][K] . B8[N][K]^T) with the 256 x 128 x 128-byte tile of tools/probes/fp8_gemm_probe.hip
 // (three LDS slots, both operands staged by buffer_load ... lds with the XOR swizzle on the source address, 8 waves of 32 x 128;
@@ -199,6 +201,41 @@ __global__ __launch_bounds__(TPB) void k_fp8_transpose_shadow(const uint8_t* __r
       }
     }
   }
+}
+
+// bf16 src [M][W] -> MX e4m3 of its TRANSPOSE: dst [W][M] + scales [W][M / 32] (= k_cast_mx8 of src^T bit for bit: the same amax, exponent,
+// multiply and conversion).  One workgroup per 32-token x 256-column tile: 16-byte loads along the source rows into an fp32 LDS image, then
+// one thread per column takes its 32 values (stride 257: conflict-free), their amax, and stores its 32 codes as two 16-byte pieces and one
+// scale byte.  grid (M / 32, ceil(W / 256)); M % 32 == 0, W % 8 == 0.
+__global__ __launch_bounds__(TPB) void k_mx8_cast_t(const __bf16* __restrict__ src, int M, int W, uint8_t* __restrict__ dst,
+                                                     uint8_t* __restrict__ sc) {
+  __shared__ float tile[32][TPB + 1];
+  const int m0 = blockIdx.x * 32, w0 = blockIdx.y * TPB, t = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = t + TPB * j, r = c >> 5, c8 = (c & 31) * 8;
+    if (w0 + c8 < W) {
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + (size_t)(m0 + r) * W + w0 + c8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) tile[r][c8 + i] = bf2f(v[i]);
+    }
+  }
+  __syncthreads();
+  const int w = w0 + t;
+  if (w >= W) return;
+  float v[32];
+  float am = 0.f;
+#pragma unroll
+  for (int r = 0; r < 32; ++r) { v[r] = tile[r][t]; am = fmaxf(am, fabsf(v[r])); }
+  const int x = mx_exp(am);
+  const float s = mx_inv(x);
+  uint32_t o[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = pack_e4m3(v[4 * i] * s, v[4 * i + 1] * s, v[4 * i + 2] * s, v[4 * i + 3] * s);
+  uint4* const d = reinterpret_cast<uint4*>(dst + (size_t)w * M + m0);
+  d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+  d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  sc[(size_t)w * (M >> 5) + (m0 >> 5)] = (uint8_t)(x + 127);
 }
 
 // ---------------------------------------------------------------- LayerNorm + modulate with the e4m3 copy (norm.hip's k_ln_mod_fwd + one store)
@@ -641,6 +678,146 @@ template __global__ void k_gemm8<E8_DG_BF16, 8>(Gemm8Args);
 template __global__ void k_gemm8<E8_DG_BF16, 9>(Gemm8Args);
 template __global__ void k_gemm8<E8_DG_GELU, 8>(Gemm8Args);
 
+// ---------------------------------------------------------------- fp8 weight gradients (sfron_fp8_wgrad)
+// C[N][K] fp32 = A[N][Mr] . B[K][Mr]^T, both operands MX e4m3 along the reduction Mr (the tokens): [rows][Mr] codes + [rows][Mr / 32] E8M0
+// bytes (k_mx8_cast_t of dY and X).  The 192 x 192 output tile of the bf16 weight-gradient GEMM (so the sum-of-squares partials keep their
+// count), 128-byte k-steps through three LDS slots filled by buffer_load ... lds (the swizzle of k_gemm8), 8 waves as 2 x 4 of 96 x 48 each.
+// A slot: A image 24 KB, B image 24 KB, then the k-step's scale bytes [192 A rows][4] and [192 B rows][4] (six 256-byte DMA pieces: waves
+// 0..5 one each, waves 6 and 7 send theirs through the zero-length descriptor to the dummy kilobyte, so every wave issues WG_NDMA pieces).
+// Both operands are read in the MX form (frag32_mx: chunks g and g + 4, lane group g's scale byte = that of 32-block g), each with its own
+// per-lane scale operand.
+struct Wgrad8Args {
+  const uint8_t *A, *a_sc, *B, *b_sc;
+  int N, K, Mr;
+  float* C; int ldc;
+  const uint8_t* sq_mask;                 // over C (element (n, k) at n * ldc + k) or null
+  double* sq_out;                         // one fp64 partial per tile (tile index tm * (K / 192) + tn), or null
+};
+constexpr int WG_T = 192, WG_NW = 8, WG_IMG = WG_T * BKB, WG_SLOT = 2 * WG_IMG + 2 * WG_T * 4;
+constexpr int WG_NP = WG_T * BKB / 1024 / WG_NW, WG_NDMA = 2 * WG_NP + 1;        // 3 + 3 16-byte pieces + 1 scale piece per wave
+constexpr size_t WG_LDS = (size_t)NSLOT8 * WG_SLOT + 1024;
+
+__global__ __launch_bounds__(512) void k_wgrad8(Wgrad8Args g) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ntn = g.K / WG_T;
+  int id;
+  {
+    const int nblk = gridDim.x, b = blockIdx.x, q = nblk >> 3, r = nblk & 7, x = b & 7, y = b >> 3;
+    id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
+  }
+  const int tm = id / ntn, tn = id - tm * ntn, m0 = tm * WG_T, n0 = tn * WG_T;
+  const int Mr = g.Mr, nk = Mr / BKB, ssz = Mr >> 5;
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, g.N * Mr, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, g.K * Mr, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsSA = __builtin_amdgcn_make_buffer_rsrc((void*)g.a_sc, 0, g.N * ssz, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsSB = __builtin_amdgcn_make_buffer_rsrc((void*)g.b_sc, 0, g.K * ssz, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsNull = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, 0, 0x00020000);
+  uint8_t* const dummy = smem8 + (size_t)NSLOT8 * WG_SLOT;
+  const int lc16 = ((lane & 7) ^ ((lane >> 3) & 7)) << 4;
+  int a_off[WG_NP], b_off[WG_NP];
+#pragma unroll
+  for (int i = 0; i < WG_NP; ++i) {
+    a_off[i] = (m0 + (wave + i * WG_NW) * 8 + (lane >> 3)) * Mr + lc16;
+    b_off[i] = (n0 + (wave + i * WG_NW) * 8 + (lane >> 3)) * Mr + lc16;
+  }
+  // scale piece of wave w < 3: A rows 64 w .. 64 w + 63; 3 <= w < 6: B rows 64 (w - 3) ..; LDS: A's [192][4] then B's [192][4]
+  const int s_off = wave < 3 ? (m0 + wave * 64 + lane) * ssz : (n0 + (wave - 3) * 64 + lane) * ssz;
+  auto issue = [&](int slot, int k0) {
+    uint8_t* iA = smem8 + slot * WG_SLOT;
+    uint8_t* iB = iA + WG_IMG;
+#pragma unroll
+    for (int i = 0; i < WG_NP; ++i) dma16b(rsA, iA + (wave + i * WG_NW) * 1024, a_off[i], k0);
+#pragma unroll
+    for (int i = 0; i < WG_NP; ++i) dma16b(rsB, iB + (wave + i * WG_NW) * 1024, b_off[i], k0);
+    if (wave < 3) dma4b(rsSA, iB + WG_IMG + wave * 256, s_off, k0 >> 5);                // wave-uniform
+    else if (wave < 6) dma4b(rsSB, iB + WG_IMG + wave * 256, s_off, k0 >> 5);
+    else dma4b(rsNull, dummy, 0, 0);
+  };
+  const int fr = lane & 15, fg = lane >> 4;
+  const int wr = wave >> 2, wc = wave & 3;          // this wave: rows wr * 96 .. + 95, columns wc * 48 .. + 47 of the tile
+  f32x4 acc[6][3];
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (nk > 0) issue(0, 0);
+  if (nk > 1) issue(1, BKB);
+  int slot = 0;
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) wait_vm<WG_NDMA>(); else wait_vm<0>();
+    __builtin_amdgcn_s_barrier();
+    if (kt + 2 < nk) issue(slot >= 1 ? slot - 1 : 2, (kt + 2) * BKB);
+    const uint8_t* iA = smem8 + slot * WG_SLOT;
+    const uint8_t* iB = iA + WG_IMG;
+    const uint8_t* iSA = iB + WG_IMG;
+    const uint8_t* iSB = iSA + WG_T * 4;
+    i32x8 fb[3];
+    int sb[3];
+#pragma unroll
+    for (int nt = 0; nt < 3; ++nt) {
+      const int rb = wc * 48 + nt * 16 + fr;
+      fb[nt] = frag32_mx(iB, rb, fg);
+      sb[nt] = iSB[rb * 4 + fg];
+    }
+    // every A fragment of the k-step is requested before the first MFMA: left to itself, hipcc sinks each mt's LDS read to its three MFMAs
+    // and waits for it there (lgkmcnt(0) six times per k-step); the scheduling barrier keeps the reads in front
+    i32x8 fa[6];
+    int sa[6];
+#pragma unroll
+    for (int mt = 0; mt < 6; ++mt) {
+      const int ra = wr * 96 + mt * 16 + fr;
+      fa[mt] = frag32_mx(iA, ra, fg);
+      sa[mt] = iSA[ra * 4 + fg];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mt = 0; mt < 6; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 3; ++nt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[nt], fa[mt], acc[mt][nt], 0, 0, 0, sb[nt], 0, sa[mt]);
+    slot = slot == 2 ? 0 : slot + 1;
+  }
+  // lane holds C[m0 + 96 wr + 16 mt + fr][n0 + 48 wc + 16 nt + 4 fg .. +3]
+  float sq = 0.f;
+  const bool sq_on = g.sq_out != nullptr;                                  // kernel-uniform
+#pragma unroll
+  for (int mt = 0; mt < 6; ++mt) {
+    const int row = m0 + wr * 96 + mt * 16 + fr;
+    uchar4 mk[3];
+    if (sq_on) {
+#pragma unroll
+      for (int nt = 0; nt < 3; ++nt)
+        mk[nt] = g.sq_mask ? *reinterpret_cast<const uchar4*>(g.sq_mask + (size_t)row * g.ldc + n0 + wc * 48 + nt * 16 + 4 * fg)
+                           : make_uchar4(1, 1, 1, 1);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 3; ++nt) {
+      const f32x4 v = acc[mt][nt];
+      *reinterpret_cast<f32x4*>(g.C + (size_t)row * g.ldc + n0 + wc * 48 + nt * 16 + 4 * fg) = v;
+      if (sq_on) {
+        const uchar4 m4 = mk[nt];
+        sq += (m4.x ? v[0] * v[0] : 0.f) + (m4.y ? v[1] * v[1] : 0.f) + (m4.z ? v[2] * v[2] : 0.f) + (m4.w ? v[3] * v[3] : 0.f);
+      }
+    }
+  }
+  if (sq_on) {
+    // (as the bf16 weight-gradient tile: fp64 from the wave sums on, the waves added in wave order -- bitwise reproducible)
+    const double d = wave_sum_d((double)sq);
+    __syncthreads();                                                       // every wave is past the main loop: the slots are free
+    double* red = reinterpret_cast<double*>(smem8);
+    if (lane == 0) red[wave] = d;
+    __syncthreads();
+    if (tid == 0) {
+      double t = red[0];
+#pragma unroll
+      for (int w2 = 1; w2 < WG_NW; ++w2) t += red[w2];
+      g.sq_out[id] = t;
+    }
+  }
+}
+
 int g_fp8_loader_waves = 0;     // process-wide form of the fp8 tiles: 4 = loader waves (sfron_gemm_loader_waves(9)); measured in the config-5 step:
                                 // 65.2 / 64.0 / 64.8 ms against 63.5 / 64.1 / 64.1 for the shared-wave form -- off
 
@@ -748,6 +925,42 @@ int sfron_cast_mx8(const uint16_t* src, int M, int N, uint8_t* dst, uint8_t* sca
   SFRON_CHECK_ARG(src && dst && scales && M > 0 && N > 0 && N % 32 == 0 && (((uintptr_t)src) & 15) == 0 && ((uintptr_t)dst & 7) == 0);
   const int64_t n = (int64_t)M * N;
   hipLaunchKernelGGL(k_cast_mx8, dim3(grid_for(n >> 3)), dim3(TPB), 0, (hipStream_t)stream, (const __bf16*)src, n, dst, scales);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_cast_mx8_t(const uint16_t* src, int M, int W, uint8_t* dst, uint8_t* scales, void* stream) {
+  SFRON_CHECK_ARG(src && dst && scales && M > 0 && W > 0 && M % 32 == 0 && W % 8 == 0);
+  SFRON_CHECK_ARG((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && (W + TPB - 1) / TPB <= 65535);
+  hipLaunchKernelGGL(k_mx8_cast_t, dim3(M / 32, (W + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, (const __bf16*)src, M, W, dst, scales);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_fp8_wgrad_supported(int N, int K, int M) {
+  return (N > 0 && K > 0 && M > 0 && N % WG_T == 0 && K % WG_T == 0 && M % BKB == 0 && (long)N * M < (1L << 31) &&
+          (long)K * M < (1L << 31)) ? 1 : 0;
+}
+
+int sfron_fp8_wgrad(const sfron_fp8_wgrad_desc* d, void* stream) {
+  SFRON_CHECK_ARG(d && d->A && d->a_scales && d->B && d->b_scales && d->c_f32);
+  if (!sfron_fp8_wgrad_supported(d->N, d->K, d->M)) return SFRON_ERR_UNSUPPORTED;
+  SFRON_CHECK_ARG(d->ldc >= d->K && d->ldc % 4 == 0 && ((uintptr_t)d->c_f32 & 15) == 0);
+  SFRON_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->B) & 15) == 0 && (((uintptr_t)d->a_scales | (uintptr_t)d->b_scales) & 3) == 0);
+  SFRON_CHECK_ARG(!d->sumsq_mask || d->sumsq_partials);
+  if (d->sumsq_mask) SFRON_CHECK_ARG(((uintptr_t)d->sumsq_mask & 3) == 0);
+  Wgrad8Args g{};
+  g.A = d->A; g.a_sc = d->a_scales; g.B = d->B; g.b_sc = d->b_scales; g.N = d->N; g.K = d->K; g.Mr = d->M;
+  g.C = d->c_f32; g.ldc = d->ldc; g.sq_mask = d->sumsq_mask; g.sq_out = d->sumsq_partials;
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = 1ull << (dev & 63);
+  if ((done.fetch_or(bit) & bit) == 0) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS) != hipSuccess)
+      return (int)hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_wgrad8, dim3((d->N / WG_T) * (d->K / WG_T)), dim3(WG_NW * 64), WG_LDS, (hipStream_t)stream, g);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

@@ -133,8 +133,8 @@ class DiT(nn.Module):
         old = self.engine
         old.drain_sweep()
         new = DitEngine(batch_size, share=old, grads=old.grads, **self._engine_args)     # same parameter AND gradient arenas
+        new._share_fp8(old)             # (raises for a batch the armed fp8 tiles do not take: the old engine stays in place, intact)
         new.probe, old.probe = old.probe, None
-        new._share_fp8(old)
         old.close()
         self.engine = new
 

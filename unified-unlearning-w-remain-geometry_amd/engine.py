@@ -61,6 +61,7 @@ class DitEngine:
         self.out_shape = (batch, c.out_channels, input_size, input_size)
         self.probe = self.wprobe = None
         self.fp8 = None
+        self.fp8_wgrad = None              # MX operand workspace of the armed fp8 weight gradients (enable_fp8_wgrad), None = bf16
         h = ctypes.c_void_p()
         check(L.sfron_aux_create(ctypes.byref(h)), "aux_create")     # side stream + events for concurrent wgrads
         self.aux = h
@@ -232,6 +233,27 @@ class DitEngine:
             self.fp8.pop("w8t", None)
             self.fp8.pop("mx", None)
 
+    def enable_fp8_wgrad(self):
+        """The qkv, proj, fc1 and fc2 weight gradients of every block on the fp8 matrix core (sfron_aux_set_fp8_wgrad): dY and the forward
+        input cast to MX e4m3 along the tokens (one E8M0 scale per 32 tokens of a column) on the weight-gradient streams, then
+        sfron_fp8_wgrad.  Biases, adaLN, the embedders and the final layer stay bf16; independent of enable_fp8.  Raises SfronError for a
+        block shape the 192 x 192 fp8 tile does not take."""
+        L, c = _lib.lib(), self.cfg
+        M, D, F = c.batch * self.tokens, c.hidden, c.mlp_hidden
+        for N, K in ((3 * D, D), (D, D), (F, D), (D, F)):          # dW[out][in] = dY[M][out]^T X[M][in]
+            if not L.sfron_fp8_wgrad_supported(N, K, M):
+                raise _lib.SfronError(f"fp8 weight gradient {N}x{K} over {M} tokens: needs 192 | {N}, 192 | {K} and 128 | {M}")
+        ws = torch.empty(L.sfron_dit_fp8_wgrad_workspace_bytes(ctypes.byref(c)), dtype=torch.uint8, device=self.device)
+        check(L.sfron_aux_set_fp8_wgrad(self.aux, ptr(ws)), "aux_set_fp8_wgrad")
+        self.fp8_wgrad = ws
+        return self
+
+    def disable_fp8_wgrad(self):
+        """Back to bf16 weight gradients: disarms the aux handle and drops the MX operands.  No-op when not enabled."""
+        if self.aux is not None:
+            check(_lib.lib().sfron_aux_set_fp8_wgrad(self.aux, None), "aux_set_fp8_wgrad(disarm)")
+        self.fp8_wgrad = None
+
     def fp8_transpose(self):
         """Transposed e4m3 shadow <- the current shadow (one launch over every block matrix, on the current stream).  Every backward pass
         of an engine with the fp8 dgrads runs it first, behind any optimizer sweep still in flight (drain_sweep): whoever wrote the shadow
@@ -280,12 +302,16 @@ class DitEngine:
         check(L.sfron_fp8_update_scales(ptr(f["amax"]), f["n"], ptr(f["scales"]), s), "fp8_update_scales")
 
     def _share_fp8(self, other):
-        """Another engine over the same parameters (another batch size / a micro-batch chain) uses the same e4m3 shadow and scales."""
+        """Another engine over the same parameters (another batch size / a micro-batch chain) uses the same e4m3 shadow and scales, and
+        takes over the fp8 dgrads and the fp8 weight gradients if ``other`` had them (the latter with MX operands of its own: its
+        weight-gradient streams may run beside the other engine's).  Raises SfronError when this engine's shapes do not fit a tile."""
         if getattr(other, "fp8", None) is not None:
             ws = _lib.lib().sfron_dit_fp8_workspace_bytes(ctypes.byref(self.cfg))
             self.fp8 = dict(other.fp8, ws=torch.empty(ws, dtype=torch.uint8, device=self.device))
             if other.fp8.get("w8t") is not None:
                 self.enable_fp8_backward(w8t=other.fp8["w8t"])
+        if getattr(other, "fp8_wgrad", None) is not None:
+            self.enable_fp8_wgrad()
 
     # ------------------------------------------------------------------ passes
     def block_sweep_setup(self):

@@ -39,21 +39,26 @@ def build_mask_arena(engine, mask):
 class DiTSFRon:
     def __init__(self, model, diffusion, lr=1e-4, forget_alpha=1e-3, grad_clip=1.0, ema_decay=0.9999, mask=None,
                  unlearn_loss="ga", forget_class=0, process_group=None, bucket_bytes=256 << 20, micro_batches=1,
-                 overlap_allreduce=False, grad_transport="fp32", method="ron", fp8=False, fp8_backward=False):
+                 overlap_allreduce=False, grad_transport="fp32", method="ron", fp8=False, fp8_backward=False,
+                 fp8_wgrad=False):
         """micro_batches = 2: each forward/backward pass runs as TWO independent half-batch chains on two HIP streams
         (own workspace, own gradient arena, own side stream); the latency-bound kernels of one chain (attention,
         LayerNorm / gate backward) then run under the GEMMs of the other.  The optimizer sweep sums the two arenas.
         fp8_backward (with fp8): the four dgrads of every block on the fp8 matrix core as well (engine.enable_fp8(backward=True)); single-chain
-        SFR-on runs without the overlapped all-reduce only -- other combinations are refused here."""
-        if fp8_backward:
-            if not fp8:
-                raise ValueError("fp8_backward=True needs fp8=True (the dgrads read the forward pass's e4m3 weight shadow)")
+        SFR-on runs without the overlapped all-reduce only -- other combinations are refused here.
+        fp8_wgrad: the four weight gradients of every block on the fp8 matrix core (engine.enable_fp8_wgrad), MX-scaled along the tokens;
+        with or without fp8, under the same refusals as fp8_backward."""
+        if fp8_backward and not fp8:
+            raise ValueError("fp8_backward=True needs fp8=True (the dgrads read the forward pass's e4m3 weight shadow)")
+        for flag, name in ((fp8_backward, "fp8_backward"), (fp8_wgrad, "fp8_wgrad")):
+            if not flag:
+                continue
             if method != "ron":
-                raise ValueError("fp8_backward=True is not supported with method 'joint'")
+                raise ValueError(f"{name}=True is not supported with method 'joint'")
             if micro_batches != 1:
-                raise ValueError("fp8_backward=True is not supported with micro_batches=2")
+                raise ValueError(f"{name}=True is not supported with micro_batches=2")
             if overlap_allreduce:
-                raise ValueError("fp8_backward=True is not supported with overlap_allreduce")
+                raise ValueError(f"{name}=True is not supported with overlap_allreduce")
         if unlearn_loss not in ("ga", "rl"):
             raise ValueError(f"unsupported unlearn_loss {unlearn_loss!r} (DiT/forget.py defines only 'ga' and 'rl')")
         # method "ron" = the SFR-on iteration (two optimizer steps); "joint" = DiT/forget.py:314-316: ONE step on
@@ -97,6 +102,12 @@ class DiTSFRon:
             model.engine.enable_fp8_backward()
         if not self.fp8_backward:
             model.engine.disable_fp8_backward()      # an engine an earlier runner armed runs bf16 dgrads under this one
+        self.fp8_wgrad = bool(fp8_wgrad)
+        if self.fp8_wgrad:
+            if model.engine.fp8_wgrad is None:
+                model.engine.enable_fp8_wgrad()
+        else:
+            model.engine.disable_fp8_wgrad()          # likewise for the weight gradients
         if unlearn_loss == "rl" and (forget_class + 100) % 1000 >= model.num_classes:
             # DiT/forget.py:275-279 hard-codes (forget_class + 100) % 1000; with fewer classes the reference's nn.Embedding
             # raises an IndexError -- so do we, up front
