@@ -448,6 +448,10 @@ int sfron_conv_wgrad_scatter_batch(const sfron_wgrad_scatter_item* items /* HOST
 
 int sfron_nchw_to_rows_bf16(const float* x, int B, int C, int HW, int c_pad, uint16_t* rows, void* stream);
 int sfron_nchw_to_rows_f32(const float* x, int B, int C, int HW, int ld, float* rows, void* stream);
+/* uint8 HWC images [B][H][W][3] -> bf16 rows [B*H*W][c_pad] (c_pad % 8 == 0, channels 3.. zero): ToTensor + Normalize(0.5, 0.5), i.e.
+ * bf16_rne((x / 255.0f - 0.5f) / 0.5f) with true fp32 divisions (DiT/forget.py:200-205); flip (uint8 [B] or NULL): flip[b] != 0 reads
+ * column W-1-w of sample b (RandomHorizontalFlip).  rows 16-byte aligned. */
+int sfron_image_u8_to_rows_bf16(const uint8_t* img, int B, int H, int W, const uint8_t* flip, int c_pad, uint16_t* rows, void* stream);
 int sfron_rows_to_nchw(const float* rows, int ld, int B, int C, int HW, float* x, void* stream);
 
 /* y = bf16( act(GroupNorm(x; groups, eps) * gamma + beta) [* drop_mask * drop_scale] ), act = swish when `swish`; x fp32 rows
@@ -645,6 +649,12 @@ int sfron_guard_finite(const float* a, const float* b, const float* c, const flo
  * [n][2c][hw] = mean || logvar -- vae.encode(x).latent_dist.sample().mul_(0.18215) of DiT/forget.py:265-267,305-307 with the
  * encoder's output cached offline (diffusers' DiagonalGaussianDistribution.sample; diffusers is absent here: parity unpinned) */
 int sfron_latent_sample(const float* moments, const float* eps, int n, int c, int hw, float scale, float* out, void* stream);
+/* VAE encoder tail: quant_conv over the fp32 conv_out rows [B*hw][ld] (z2 = 2z <= 16 columns read): m[o] = bias[o] + sum_i w[o][i] x[i] as
+ * fp32 FMAs in ascending i (w = quant_conv.weight [z2][z2][1][1]).  Writes the posterior moments NCHW [B][z2][hw] (mean || logvar) to
+ * moments_f32 and / or moments_f16 (RNE); with eps [B][z2/2][hw] also latent [B][z2/2][hw] = sfron_latent_sample of the fp32 moments, bit
+ * for bit (eps and latent both NULL or both set). */
+int sfron_vae_moments(const float* rows, int ld, int B, int hw, int z2, const float* w, const float* bias, float* moments_f32,
+                      uint16_t* moments_f16, const float* eps, float scale, float* latent, void* stream);
 /* NCHW fp32 image -> bf16 token rows [n*T][C*p*p]; chan_last 0: k = c*p*p + ph*p + pw (Conv2d weight order,
  * timm PatchEmbed); 1: k = (ph*p + pw)*C + c (unpatchify order, DiT/models.py:218-231) */
 int sfron_patchify(const float* img, int n, int C, int H, int W, int p, int chan_last, uint16_t* rows, int ld, void* stream);

@@ -886,6 +886,26 @@ __global__ __launch_bounds__(TPB) void k_nchw_to_rows(const float* __restrict__ 
     rows[i] = c < C ? f2bf(x[((int64_t)b * C + c) * HW + hw]) : (__bf16)0.0f;
   }
 }
+// uint8 HWC images (the PIL loader's arrays) -> bf16 rows [B*H*W][Cp], Cp % 8 == 0, channels 3.. zero: ToTensor + Normalize(0.5, 0.5)
+// as DiT/forget.py:200-205 computes it, (x / 255 - 0.5) / 0.5 in fp32 with true divisions, then RNE; flip[b] != 0 mirrors sample b
+// (RandomHorizontalFlip: output column w reads source column W-1-w).  One thread per pixel, 16-byte stores.
+__global__ __launch_bounds__(TPB) void k_image_u8_to_rows(const uint8_t* __restrict__ img, int B, int H, int W, const uint8_t* __restrict__ flip,
+                                                          int Cp, __bf16* __restrict__ rows) {
+  const int64_t n = (int64_t)B * H * W;
+  for (int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x; p < n; p += (int64_t)gridDim.x * TPB) {
+    const int w = (int)(p % W); const int64_t bh = p / W; const int b = (int)(bh / H);
+    const int ws = (flip && flip[b]) ? W - 1 - w : w;
+    const uint8_t* px = img + (bh * W + ws) * 3;
+    bf16x8 v;
+    for (int c = 0; c < 8; ++c) v[c] = (__bf16)0.0f;
+    for (int c = 0; c < 3; ++c) v[c] = f2bf(((float)px[c] / 255.0f - 0.5f) / 0.5f);
+    bf16x8* out = reinterpret_cast<bf16x8*>(rows + p * Cp);
+    out[0] = v;
+    bf16x8 z;
+    for (int c = 0; c < 8; ++c) z[c] = (__bf16)0.0f;
+    for (int g = 1; g < Cp / 8; ++g) out[g] = z;
+  }
+}
 __global__ __launch_bounds__(TPB) void k_rows_to_nchw(const float* __restrict__ rows, int ld, int B, int C, int HW, float* __restrict__ x) {
   const int64_t n = (int64_t)B * C * HW;
   for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
@@ -2472,6 +2492,13 @@ int sfron_conv_wgrad_scatter_batch(const sfron_wgrad_scatter_item* items, int n_
 int sfron_nchw_to_rows_bf16(const float* x, int B, int C, int HW, int c_pad, uint16_t* rows, void* stream) {
   SFRON_CHECK_ARG(x && rows && c_pad >= C);
   hipLaunchKernelGGL(k_nchw_to_rows, dim3(grid_for((int64_t)B * HW * c_pad)), dim3(TPB), 0, (hipStream_t)stream, x, B, C, HW, c_pad, (__bf16*)rows);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+int sfron_image_u8_to_rows_bf16(const uint8_t* img, int B, int H, int W, const uint8_t* flip, int c_pad, uint16_t* rows, void* stream) {
+  SFRON_CHECK_ARG(img && rows && B > 0 && H > 0 && W > 0 && c_pad >= 8 && c_pad % 8 == 0 && ((uintptr_t)rows & 15) == 0);
+  hipLaunchKernelGGL(k_image_u8_to_rows, dim3(grid_for((int64_t)B * H * W)), dim3(TPB), 0, (hipStream_t)stream, img, B, H, W, flip, c_pad,
+                     (__bf16*)rows);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

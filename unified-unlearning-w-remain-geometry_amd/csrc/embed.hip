@@ -165,6 +165,38 @@ __global__ __launch_bounds__(TPB) void k_latent_sample(const float* __restrict__
   }
 }
 
+// The VAE encoder's tail: quant_conv (a 1x1 conv, 2z x 2z + bias) over the fp32 conv_out rows [B*hw][ld], one thread per pixel.
+// acc = bias[o], then acc = fma(w[o][i], x[i], acc) for i ascending (fixed order).  Writes the posterior moments NCHW [B][2z][hw] as
+// fp32 and / or fp16 (RNE), and optionally the latent of k_latent_sample from the fp32 values, in its expression (bit-identical).
+__global__ __launch_bounds__(TPB) void k_vae_moments(const float* __restrict__ rows, int ld, int B, int hw, int z2, const float* __restrict__ w,
+                                                     const float* __restrict__ bias, float* __restrict__ mom, _Float16* __restrict__ mom16,
+                                                     const float* __restrict__ eps, float scale, float* __restrict__ lat) {
+  const int64_t n = (int64_t)B * hw;
+  const int c = z2 / 2;
+  for (int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x; p < n; p += (int64_t)gridDim.x * TPB) {
+    const int64_t b = p / hw, r = p - b * hw;
+    float x[16], m[16];
+    for (int i = 0; i < z2; ++i) x[i] = rows[p * ld + i];
+    for (int o = 0; o < z2; ++o) {
+      float acc = bias[o];
+      for (int i = 0; i < z2; ++i) acc = fmaf(w[o * z2 + i], x[i], acc);
+      m[o] = acc;
+      const int64_t at = (b * z2 + o) * hw + r;
+      if (mom) mom[at] = acc;
+      if (mom16) mom16[at] = (_Float16)acc;
+    }
+    if (lat) {
+      for (int o = 0; o < c; ++o) {
+        const int64_t i = (b * c + o) * hw + r;
+        const float mean = m[o];
+        float lv = m[c + o];
+        lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+        lat[i] = (mean + expf(0.5f * lv) * eps[i]) * scale;
+      }
+    }
+  }
+}
+
 inline int grid_for(int64_t n) {
   int64_t b = (n + TPB - 1) / TPB;
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -225,6 +257,16 @@ extern "C" {
 int sfron_latent_sample(const float* moments, const float* eps, int n, int c, int hw, float scale, float* out, void* stream) {
   SFRON_CHECK_ARG(moments && eps && out && n > 0 && c > 0 && hw > 0);
   hipLaunchKernelGGL(k_latent_sample, dim3(grid_for((int64_t)n * c * hw)), dim3(TPB), 0, (hipStream_t)stream, moments, eps, n, c, hw, scale, out);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_vae_moments(const float* rows, int ld, int B, int hw, int z2, const float* w, const float* bias, float* moments_f32,
+                      uint16_t* moments_f16, const float* eps, float scale, float* latent, void* stream) {
+  SFRON_CHECK_ARG(rows && w && bias && B > 0 && hw > 0 && z2 > 0 && z2 % 2 == 0 && z2 <= 16 && ld >= z2);
+  SFRON_CHECK_ARG((moments_f32 || moments_f16 || latent) && (latent == nullptr) == (eps == nullptr));
+  hipLaunchKernelGGL(k_vae_moments, dim3(grid_for((int64_t)B * hw)), dim3(TPB), 0, (hipStream_t)stream, rows, ld, B, hw, z2, w, bias, moments_f32,
+                     (_Float16*)moments_f16, eps, scale, latent);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

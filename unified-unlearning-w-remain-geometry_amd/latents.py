@@ -7,14 +7,20 @@ the remain set is every other class) and encodes each image batch with the froze
 its OUTPUT is cached once, offline, as the posterior moments (mean || logvar, [8, 32, 32] fp16/fp32 per image) in per-class
 shards, and the step's inputs come from that cache: the class split is the reference's, the posterior sample + 0.18215
 scaling is sfron_latent_sample on the device, and batches reach the GPU through pinned buffers on a copy stream one batch
-ahead of the step (data-parallel ranks take strided shares of each global batch).  The VAE itself (diffusers AutoencoderKL,
-absent here) is outside the path: ``write_shard`` takes whatever moments the caller's encoder produced.
+ahead of the step (data-parallel ranks take strided shares of each global batch).  ``write_shard`` takes whatever moments the
+caller's encoder produced; ``encode_image_folder`` fills the cache from an ImageFolder with the native encoder (sfron.vae).
+
+The online route, ``UnlearnImageLoader``, is the reference's loop with the encode included: decode + centre crop on host threads,
+RandomHorizontalFlip drawn per sample, and the KL-f8 encoder + posterior sample on the device in each ``next()``.  It enumerates and
+draws like the cache route, so one seed gives both routes the same batches (flips aside).
 """
+from concurrent.futures import ThreadPoolExecutor
 import json
 import os
 
 import numpy as np
 import torch
+from PIL import Image
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
@@ -77,6 +83,23 @@ class LatentCache:
         return [(c, self.index[c]["index"], i) for c in names for i in range(self.index[c]["count"])]
 
 
+def _batch_draws(seed, stream, step, n_samples, gb, num_timesteps, drop_prob, C, h, w):
+    """The host draws of one global batch: (sample ids, t, noise, eps, drop, g2), keyed by (seed, epoch / step, stream).  Shuffling is
+    per epoch (drop_last), the per-step generator g2 draws t, noise, posterior eps and the label-dropout mask in that order; a caller
+    that needs more draws (the image loader's flips) takes them from g2 after these."""
+    per_epoch = max(1, n_samples // gb)                                          # drop_last, as the reference's loaders
+    epoch, pos = divmod(step, per_epoch)
+    g = torch.Generator().manual_seed(((seed * 1_000_003 + epoch) * 2 + (stream == "remain")) & 0x7FFFFFFF)
+    perm = torch.randperm(n_samples, generator=g)
+    ids = perm[pos * gb:(pos + 1) * gb] if n_samples >= gb else perm[torch.arange(gb) % n_samples]
+    g2 = torch.Generator().manual_seed(((seed * 7_000_003 + step) * 2 + (stream == "remain")) & 0x7FFFFFFF)
+    t = torch.randint(0, num_timesteps, (gb,), generator=g2)
+    noise = torch.randn(gb, C, h, w, generator=g2)
+    eps = torch.randn(gb, C, h, w, generator=g2)
+    drop = (torch.rand(gb, generator=g2) < drop_prob).to(torch.uint8)
+    return ids, t, noise, eps, drop, g2
+
+
 class UnlearnLatentLoader:
     """Infinite forget / remain batch streams for DiTSFRon.step (the reference cycles two shuffled DataLoaders,
     DiT/forget.py:219-228,241-246): each ``next()`` returns ``dict(x0, y, t, noise, drop)`` on the device for this rank's share
@@ -98,18 +121,8 @@ class UnlearnLatentLoader:
 
     def _host_batch(self, stream, step):
         s = self.sets[stream]
-        per_epoch = max(1, len(s) // self.gb)                                   # drop_last, as the reference's loaders
-        epoch, pos = divmod(step, per_epoch)
-        g = torch.Generator().manual_seed(((self.seed * 1_000_003 + epoch) * 2 + (stream == "remain")) & 0x7FFFFFFF)
-        perm = torch.randperm(len(s), generator=g)
-        ids = perm[pos * self.gb:(pos + 1) * self.gb] if len(s) >= self.gb else perm[torch.arange(self.gb) % len(s)]
-        g2 = torch.Generator().manual_seed(((self.seed * 7_000_003 + step) * 2 + (stream == "remain")) & 0x7FFFFFFF)
         shp = self.cache.index[s[0][0]]["shape"]
-        C = shp[0] // 2
-        t = torch.randint(0, self.T, (self.gb,), generator=g2)
-        noise = torch.randn(self.gb, C, shp[1], shp[2], generator=g2)
-        eps = torch.randn(self.gb, C, shp[1], shp[2], generator=g2)
-        drop = (torch.rand(self.gb, generator=g2) < self.p).to(torch.uint8)
+        ids, t, noise, eps, drop, _ = _batch_draws(self.seed, stream, step, len(s), self.gb, self.T, self.p, shp[0] // 2, shp[1], shp[2])
         mine = list(range(self.rank, self.gb, self.world))                     # strided share of the global batch
         mom = np.stack([np.asarray(self.cache.shard(s[int(ids[j])][0])[s[int(ids[j])][2]], dtype=np.float32) for j in mine])
         y = torch.tensor([s[int(ids[j])][1] for j in mine], dtype=torch.int64)
@@ -146,4 +159,131 @@ class UnlearnLatentLoader:
         x0 = torch.empty(n, c2 // 2, h, w, dtype=torch.float32, device=mom.device)
         check(_lib.lib().sfron_latent_sample(ptr(mom), ptr(dv["eps"]), n, c2 // 2, h * w, float(self.scale), ptr(x0), stream_ptr()),
               "latent_sample")
+        return dict(x0=x0, y=dv["y"], t=dv["t"], noise=dv["noise"], drop=dv["drop"])
+
+
+# ------------------------------------------------------------------------------------------------ image front-end
+MAX_HOST_THREADS = 16      # a GPU host gives one command 16 CPUs
+
+
+def center_crop_arr(pil_image, image_size):
+    """ADM's centre crop as DiT/forget.py:89-107 uses it: halve with a BOX filter while the short side is >= 2 x image_size, resize
+    with BICUBIC so the short side is image_size (sizes rounded), then crop the centre image_size x image_size."""
+    img = pil_image
+    while min(img.size) >= 2 * image_size:
+        img = img.resize(tuple(d // 2 for d in img.size), resample=Image.BOX)
+    s = image_size / min(img.size)
+    img = img.resize(tuple(round(d * s) for d in img.size), resample=Image.BICUBIC)
+    a = np.array(img)
+    top, left = (a.shape[0] - image_size) // 2, (a.shape[1] - image_size) // 2
+    return Image.fromarray(a[top:top + image_size, left:left + image_size])
+
+
+def class_files(directory):
+    """torchvision's make_dataset order for one class directory: os.walk (followlinks) in sorted order, file names sorted, image extensions."""
+    out = []
+    for root, _, fnames in sorted(os.walk(directory, followlinks=True)):
+        for f in sorted(fnames):
+            if f.lower().endswith(IMG_EXTENSIONS):
+                out.append(os.path.join(root, f))
+    return out
+
+
+def load_image(path, image_size):
+    """pil_loader (RGB) + center_crop_arr -> uint8 [image_size, image_size, 3]."""
+    with open(path, "rb") as fh:
+        img = Image.open(fh).convert("RGB")
+    return np.asarray(center_crop_arr(img, image_size), dtype=np.uint8)
+
+
+def _pool(workers):
+    return ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_HOST_THREADS)))
+
+
+def encode_image_folder(data_path, encoder, cache_dir, image_size=256, batch=32, dtype=np.float32, workers=8):
+    """``data_path/train/<class>/*`` -> one write_shard per class of the encoder's posterior moments (what LatentCache and
+    UnlearnLatentLoader read), files in ImageFolder order.  Images are decoded and cropped on a host thread pool while the
+    previous batch encodes on the device.  Returns {class name: image count}."""
+    classes, class_to_idx = find_classes(os.path.join(data_path, "train"))
+    mdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[np.dtype(dtype)]
+    counts = {}
+    with _pool(workers) as pool:
+        for c in classes:
+            files = class_files(os.path.join(data_path, "train", c))
+            parts = []
+            nxt = pool.map(lambda f: load_image(f, image_size), files[:batch]) if files else None
+            for lo in range(0, len(files), batch):
+                imgs = np.stack(list(nxt))
+                nxt = pool.map(lambda f: load_image(f, image_size), files[lo + batch:lo + 2 * batch]) if lo + batch < len(files) else None
+                parts.append(encoder.moments(torch.from_numpy(imgs), dtype=mdt).cpu().numpy())
+            if not parts:
+                raise FileNotFoundError(f"class {c!r} has no image files")
+            write_shard(cache_dir, c, class_to_idx[c], np.concatenate(parts))
+            counts[c] = len(files)
+    return counts
+
+
+class UnlearnImageLoader:
+    """UnlearnLatentLoader's contract -- ``next(stream)`` gives ``dict(x0, y, t, noise, drop)`` on the device for this rank's strided share
+    of a global batch -- with the images read from ``data_path/train`` and encoded on the GPU in the call (DiT/forget.py:200-246,
+    265-267,305-307: centre crop, RandomHorizontalFlip, ToTensor + Normalize, vae.encode(x).latent_dist.sample().mul_(0.18215)).
+    Sample ids, shuffling and the t / noise / eps / drop draws equal the cache route's; the flips are drawn after them, so with
+    ``flip_prob=0`` every field but x0 equals UnlearnLatentLoader's bit for bit.  The next batch is decoded on host threads and copied
+    on a side stream while the current one is consumed."""
+
+    def __init__(self, data_path, forget_class, encoder, global_batch, rank=0, world=1, seed=0, image_size=256, flip_prob=0.5,
+                 num_timesteps=1000, drop_prob=0.1, scale=0.18215, device="cuda", workers=8):
+        assert global_batch % world == 0
+        self.enc, self.gb, self.rank, self.world, self.seed = encoder, global_batch, rank, world, seed
+        self.size, self.flip_prob, self.T, self.p, self.scale = image_size, float(flip_prob), num_timesteps, drop_prob, scale
+        self.dev = torch.device(device)
+        f = 1 << (len(encoder.ch_mult) - 1)
+        self.lat_shape = (encoder.z, image_size // f, image_size // f)
+        forget, remain, class_to_idx = class_split(data_path, forget_class)
+        root = os.path.join(data_path, "train")
+        samples = lambda names: [(p, class_to_idx[c]) for c in names for p in class_files(os.path.join(root, c))]
+        self.sets = {"forget": samples(forget), "remain": samples(remain)}
+        if not self.sets["forget"] or not self.sets["remain"]:
+            raise ValueError("empty forget or remain set")
+        self.step = {"forget": 0, "remain": 0}
+        self._copy = torch.cuda.Stream(device=self.dev)
+        self._pool = _pool(workers)                # decodes the images of a batch
+        self._bg = ThreadPoolExecutor(max_workers=1)   # assembles the next batch (its own thread: it waits on _pool's tasks)
+        self._ahead, self._pinned = {}, None
+
+    def _host_batch(self, stream, step):
+        s = self.sets[stream]
+        C, h, w = self.lat_shape
+        ids, t, noise, eps, drop, g2 = _batch_draws(self.seed, stream, step, len(s), self.gb, self.T, self.p, C, h, w)
+        flip = (torch.rand(self.gb, generator=g2) < self.flip_prob).to(torch.uint8)
+        mine = list(range(self.rank, self.gb, self.world))
+        imgs = np.stack(list(self._pool.map(lambda j: load_image(s[int(ids[j])][0], self.size), mine)))
+        y = torch.tensor([s[int(ids[j])][1] for j in mine], dtype=torch.int64)
+        return dict(images=torch.from_numpy(imgs), flip=flip[mine].contiguous(), eps=eps[mine].contiguous(), y=y, t=t[mine].contiguous(),
+                    noise=noise[mine].contiguous(), drop=drop[mine].contiguous())
+
+    def _stage(self, hb):
+        pinned = {k: v.pin_memory() for k, v in hb.items()}
+        with torch.cuda.stream(self._copy):
+            dv = {k: v.to(self.dev, non_blocking=True) for k, v in pinned.items()}
+            ev = torch.cuda.Event()
+            ev.record(self._copy)
+        return dv, (ev, pinned)
+
+    def host_batch(self, stream, step):
+        """The host side of batch `step` of `stream` (uint8 images [n, S, S, 3], flips and the draws), for tests and tools."""
+        return self._host_batch(stream, step)
+
+    def next(self, stream):
+        step = self.step[stream]
+        fut = self._ahead.pop((stream, step), None)
+        hb = fut.result() if fut is not None else self._host_batch(stream, step)
+        self._ahead[(stream, step + 1)] = self._bg.submit(self._host_batch, stream, step + 1)     # decode one batch ahead
+        self.step[stream] = step + 1
+        dv, (ev, self._pinned) = self._stage(hb)     # (the pinned batch lives until the next call)
+        cur = torch.cuda.current_stream()
+        cur.wait_event(ev)
+        for v in dv.values():
+            v.record_stream(cur)
+        x0 = self.enc.encode(dv["images"], eps=dv["eps"], flip=dv["flip"], scale=self.scale)
         return dict(x0=x0, y=dv["y"], t=dv["t"], noise=dv["noise"], drop=dv["drop"])
