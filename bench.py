@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SFR-on unlearning steps/sec, DiT-XL/2 256 px, batch 32 per GPU (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" = one full SFR-on iteration (DiT/forget.py:256-322): forget fwd/bwd -> mask -> clip -> AdamW,
@@ -14,7 +14,11 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                     weight-gradient stream it is launched on (all four GEMMs of every 9th block of every backward pass inside
                     the timed region); "others" holds the same measurement for the fc1 forward GEMM (main stream) and an "hbm"
                     entry for the parameter sweep k_masked_clip_adam
-  "cpu_baseline" -- the oracle (plain PyTorch fp32, CPU) timed on a bounded sample on this box's host cores.
+  "cpu_baseline" -- (--full) the oracle (plain PyTorch fp32, CPU) timed on a bounded sample on this box's host cores.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  --full adds what
+takes work of its own after the timed region: the CPU baseline, the bounded runs of BASELINE configs 1, 2, 4, 5
+(roofline.others.configs), two extra steps that time the remain-stage sweep whole when the timed steps split it (roofline.others.hbm),
+and with N > 1 the data-parallel evidence block ("dp").
 With N > 1 the overlapped gradient exchange is switched on only after DiTSFRon.verify_overlap() has reproduced the synchronous
 exchange on the ranks of this very run ("dp_overlap" in the JSON says which path was timed).
 """
@@ -43,7 +47,10 @@ def parse():
     ap.add_argument("--model", default="DiT-XL/2")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--image-size", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the CPU baseline, the bounded runs of BASELINE configs 1, 2, 4, 5, "
+                         "two extra steps that time the remain-stage sweep whole, and (N > 1) the data-parallel evidence block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--micro-batches", type=int, default=1, help="independent half-batch chains per pass (1 or 2)")
     ap.add_argument("--cpu-batch", type=int, default=8, help="batch of the bounded CPU-baseline sample")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: keep the synchronous bucketed all-reduce")
@@ -57,12 +64,12 @@ def parse():
     ap.add_argument("--grad-transport", default="auto", choices=("auto", "fp32", "bf16"),
                     help="N > 1: precision of the gradient exchange; auto = bf16 from four ranks on, the exact fp32 sum below that")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the bounded runs of BASELINE configs 1, 2, 4, 5 behind the headline region (roofline.others.configs)")
+                    help="with --full: skip the bounded runs of BASELINE configs 1, 2, 4, 5 behind the headline region (roofline.others.configs)")
     ap.add_argument("--check", action="store_true",
                     help="N-rank == 1-rank parity: after the run every rank also computes the gradient of the WHOLE global batch "
                          "of step 0 by itself and compares it with the all-reduced gradient of the sharded run")
     ap.add_argument("--no-dp-evidence", action="store_true",
-                    help="N > 1: skip the default self-verification block of the JSON line (device identities, linearity check of the "
+                    help="N > 1 with --full: skip the self-verification block of the JSON line (device identities, linearity check of the "
                          "exchange, replica checksums, all-reduce timing)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: its per-sample losses, "
@@ -304,7 +311,7 @@ def other_configs(dev, latent, budget_s=75.0):
 
 def dp_evidence(runner, model, diff, batch0, dev, rank, world, strict_tol=None):
     """What a reader of the JSON line needs to see that N ranks on N DEVICES exchanged gradients correctly, collected on
-    every multi-rank run by default, AFTER the timed region:
+    every multi-rank --full run, AFTER the timed region:
       devices            every rank's (host, device UUID / PCI bus id), all-gathered; `distinct_devices` must equal world_size
       linearity          the exchange is a SUM: a strided sample of this rank's LOCAL gradient (plain backward pass, no exchange) is
                          all-gathered, summed over ranks in fp64 and compared with the same sample of the EXCHANGED gradient the runner's
@@ -519,7 +526,10 @@ def main():
     n_wp, wp_ms = eng.wgrad_probe_read()
     sched_across = bool(runner.sweep_across_steps and runner.sweep_beside_forward)      # as the timed region ran (data-parallel ranks too)
     sweep_where = "inside the timed region"
-    if not any(whole for _, _, whole in runner.opt.timed) and world == 1:
+    split_sweep = not any(whole for _, _, whole in runner.opt.timed) and world == 1
+    if split_sweep and not args.full:
+        sweep_where = "not measured: the timed region splits the sweep across the step boundary; --full times it whole on two extra steps"
+    elif split_sweep:
         # the remain-stage sweep of the blocks ran split across the step boundary (config.schedule): for the `others.hbm` roofline time
         # it WHOLE -- one launch sequence on one stream -- on two extra steps after the timed region
         runner.sync_sweep()
@@ -586,7 +596,7 @@ def main():
     sweep_traffic, sweep_alg, sweep_traffic_note = sane_sweep_traffic()
 
     dp_ev = None
-    if world > 1 and not args.no_dp_evidence and args.micro_batches == 1:
+    if args.full and world > 1 and not args.no_dp_evidence and args.micro_batches == 1:
         wd.phase("dp evidence", 180 + 8 * step_budget)
         try:
             dp_ev = dp_evidence(runner, model, diff, batches[0][0], dev, rank, world)
@@ -620,6 +630,7 @@ def main():
             # whole-job aggregate: every rank runs batch-32 steps (weak scaling), so the job does world * steps of them in `elapsed`
             # (one synchronous iteration over the global batch of 32 * world samples takes ms_per_step)
             "value": world * args.steps / elapsed, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "fp8_e4m3 forward GEMMs (weights + activations), bf16 backward GEMMs, fp32 accumulate" if args.fp8 else "bf16",
             "data": "synthetic",
@@ -659,7 +670,7 @@ def main():
                                      "bytes_per_launch": sweep_bytes, "avg_launch_ms": sw_ms, "launches_timed": len(sweep_ms),
                                      "measured": sweep_where}}},
         }
-        if world == 1 and not args.no_configs and args.model == "DiT-XL/2" and not args.fp8:
+        if args.full and world == 1 and not args.no_configs and args.model == "DiT-XL/2" and not args.fp8:
             # the other BASELINE configurations, on the same box right after the headline: free the headline's arenas first
             import gc
             runner.sync_sweep()
@@ -668,7 +679,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             res["roofline"]["others"]["configs"] = other_configs(dev, latent)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(args.model, latent, args.batch, args.cpu_batch)
         else:
             res["cpu_baseline"] = None

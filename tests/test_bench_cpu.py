@@ -105,6 +105,17 @@ def test_steps_below_one_is_refused(monkeypatch):
     assert a.steps == 3 and a.dump_outputs == "d"
 
 
+def test_plain_run_is_lean_unless_full(monkeypatch):
+    """What the headline does not need (CPU baseline, other configs, the whole-sweep steps, the dp evidence) runs only with --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--no-configs"])
+    a = bench.parse()
+    assert a.full and a.no_configs and not a.no_cpu_baseline
+
+
 def test_dump_outputs_writes_float_arrays_of_the_last_step_within_the_cap(tmp_path):
     """--dump-outputs on a stand-in runner (CPU tensors): every array is float32 / float64, the state sample is drawn at the same seeded
     positions on every call, and the whole dump stays under the cap."""

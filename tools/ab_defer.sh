@@ -17,4 +17,4 @@ for rep in 1 2; do
   done
 done
 echo "=== default run, legs config2,config5" | tee -a $out/log.txt
-SFRON_BENCH_LEGS=config2,config5 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>$out/legs.err | tee $out/legs.json | line | tee -a $out/log.txt
+SFRON_BENCH_LEGS=config2,config5 timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>$out/legs.err | tee $out/legs.json | line | tee -a $out/log.txt

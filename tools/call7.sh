@@ -12,7 +12,7 @@ for l in sys.stdin:
 "
 done
 timeout -k 10 400 python3 tools/bench_dp_footprint.py 10 > $out/dp_footprint.txt 2>&1; tail -10 $out/dp_footprint.txt
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>$out/bench_full.err | tee $out/bench_full.json | python3 -c "
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>$out/bench_full.err | tee $out/bench_full.json | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -22,5 +22,5 @@ for n in 20 100; do
 done
 for order in config5,config2 config2,config5; do
   echo "=== default run, legs $order" | tee -a $out/log.txt
-  SFRON_BENCH_LEGS=$order timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>$out/legs_$order.err | tee $out/legs_$order.json | line | tee -a $out/log.txt
+  SFRON_BENCH_LEGS=$order timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>$out/legs_$order.err | tee $out/legs_$order.json | line | tee -a $out/log.txt
 done

@@ -12,7 +12,7 @@ out, tag = os.path.abspath(sys.argv[1]), sys.argv[2]
 os.makedirs(out, exist_ok=True)
 env = dict(os.environ, TMPDIR="/tmp")
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    subprocess.run(["rocprofv3", "--pmc", c, "--output-format", "csv", "-d", os.path.join(out, c), "--", "python3", os.path.join(ROOT, "bench.py"),
+    subprocess.run(["rocprofv3", "--pmc", c, "--output-format", "csv", "-d", os.path.join(out, c), "--", "python3", os.path.join(ROOT, "bench.py"), "--full",
                     "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-configs"], cwd="/tmp", env=env, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 agg = collections.defaultdict(lambda: [0.0, 0])
 for path in glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True):
@@ -35,7 +35,7 @@ for (c, k), (sm, n) in agg.items():
     if any(x in k for x in ("k_masked_clip_adam", "k_adam_lowrank", "k_sumsq_masked", "k_sumsq_lowrank", "k_sumsq_ranges")):
         tot[c] += sm
 # steps in the profiled run: NOT the 3 of the command line -- when the timed steps split their remain-stage sweep across the step boundary,
-# bench.py appends two more steps to time that sweep whole (round 3 divided by 3 and reported 5/3 of the traffic: 78.7 GB against 47.2 GB
+# bench.py --full appends two more steps to time that sweep whole (round 3 divided by 3 and reported 5/3 of the traffic: 78.7 GB against 47.2 GB
 # algorithmic, which would have been more than the HBM peak).  k_adam_lowrank runs exactly twice per step (forget + remain stage).
 n_lowrank = max([n for (c, k), (sm, n) in agg.items() if c == "FETCH_SIZE" and "k_adam_lowrank" in k] or [0])
 n_steps = n_lowrank / 2.0 if n_lowrank else 3.0
