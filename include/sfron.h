@@ -453,6 +453,19 @@ int sfron_nchw_to_rows_f32(const float* x, int B, int C, int HW, int ld, float* 
  * column W-1-w of sample b (RandomHorizontalFlip).  rows 16-byte aligned. */
 int sfron_image_u8_to_rows_bf16(const uint8_t* img, int B, int H, int W, const uint8_t* flip, int c_pad, uint16_t* rows, void* stream);
 int sfron_rows_to_nchw(const float* rows, int ld, int B, int C, int HW, float* x, void* stream);
+/* VAE decoder tail: fp32 rows [B*H*W][ld] (ld >= 3; channels 0..2 read) -> uint8 RGB, every step a separately rounded fp32 operation.
+ *   SFRON_IMAGE_SAVE_IMAGE (torchvision make_grid(normalize=True, value_range=(lo, hi)) + save_image; hi > lo):
+ *     v = (clamp(x, lo, hi) - lo) / (hi - lo);  u = trunc(clamp(v * 255 + 0.5, 0, 255))   (v * 255 and + 0.5 rounded in that order)
+ *   SFRON_IMAGE_ROUND (diffusers / SD generate-images.py; lo, hi unused):  v = clamp(x / 2 + 0.5, 0, 1);  u = rint_half_even(v * 255)
+ * The rows hold samples b0 .. b0+B-1 of a batch of n (n >= b0 + B; a chunked decode launches once per chunk).
+ *   nrow == 0: out = [n][H][W][3]; this launch writes its B samples.
+ *   nrow > 0:  out = the make_grid canvas [Hc][Wc][3]: xmaps = min(nrow, n) columns, ceil(n / xmaps) rows, cells (H + padding) x
+ *              (W + padding) behind a padding-pixel outer border, Hc = rows * (H + padding) + padding (Wc alike); pad pixels and empty
+ *              cells are byte 0 and are written by the launch with b0 == 0.  n == 1 gives the bare H x W image.
+ * Hc * Wc * 3 (or B * H * W * 3) < 2^31. */
+enum { SFRON_IMAGE_SAVE_IMAGE = 0, SFRON_IMAGE_ROUND = 1 };
+int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int mode, float lo, float hi, int nrow, int padding, int b0, int n,
+                           uint8_t* out, void* stream);
 
 /* y = bf16( act(GroupNorm(x; groups, eps) * gamma + beta) [* drop_mask * drop_scale] ), act = swish when `swish`; x fp32 rows
  * [B * HW][ldx]; mean / rstd [B][groups] saved for the backward pass (models/diffusion.py:43-46,126-131) */
@@ -655,6 +668,12 @@ int sfron_latent_sample(const float* moments, const float* eps, int n, int c, in
  * for bit (eps and latent both NULL or both set). */
 int sfron_vae_moments(const float* rows, int ld, int B, int hw, int z2, const float* w, const float* bias, float* moments_f32,
                       uint16_t* moments_f16, const float* eps, float scale, float* latent, void* stream);
+/* VAE decoder head: post_quant_conv(z / scale) over the NCHW fp32 latents z [B][zc][hw] (zc <= 16): x = z / scale (correctly rounded
+ * fp32 division), y[p][o] = bias[o] + sum_{c = 0..zc-1} w[o][c] * x[c] in that order, each product and sum rounded separately (w =
+ * post_quant_conv.weight [zc][zc][1][1]).  Writes bf16 rows [B*hw][c_pad] (RNE; c_pad >= zc, c_pad % 8 == 0, channels zc.. zero) -- what
+ * conv_in reads -- and, when rows_f32 is set, the same values [B*hw][c_pad] in fp32 before the rounding.  Both 16-byte aligned. */
+int sfron_vae_latent_in(const float* z, int B, int zc, int hw, const float* w, const float* bias, float scale, int c_pad, uint16_t* rows,
+                        float* rows_f32, void* stream);
 /* NCHW fp32 image -> bf16 token rows [n*T][C*p*p]; chan_last 0: k = c*p*p + ph*p + pw (Conv2d weight order,
  * timm PatchEmbed); 1: k = (ph*p + pw)*C + c (unpatchify order, DiT/models.py:218-231) */
 int sfron_patchify(const float* img, int n, int C, int H, int W, int p, int chan_last, uint16_t* rows, int ld, void* stream);

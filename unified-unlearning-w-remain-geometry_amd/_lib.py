@@ -100,6 +100,7 @@ _PROTOS.update({
     "sfron_timestep_embed": (c_int, [_P, c_int, c_int, _P, c_int, _S]),
     "sfron_latent_sample": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _S]),
     "sfron_vae_moments": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _S]),
+    "sfron_vae_latent_in": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _S]),
     "sfron_guard_inputs": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _S]),
     "sfron_guard_finite": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _S]),
     "sfron_silu_fwd": (c_int, [_P, c_int64, _P, _S]),
@@ -211,6 +212,7 @@ _PROTOS.update({
     "sfron_nchw_to_rows_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _S]),
     "sfron_image_u8_to_rows_bf16": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _S]),
     "sfron_rows_to_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _S]),
+    "sfron_rows_to_image_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, _P, _S]),
     "sfron_groupnorm_fwd": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_float, _P, _P, _P, _P, _S]),
     "sfron_groupnorm_bwd": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, c_int, c_int,
                                     _P, _P, _P, _S]),

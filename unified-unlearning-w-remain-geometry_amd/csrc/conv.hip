@@ -906,6 +906,61 @@ __global__ __launch_bounds__(TPB) void k_image_u8_to_rows(const uint8_t* __restr
     for (int g = 1; g < Cp / 8; ++g) out[g] = z;
   }
 }
+// The VAE decoder's tail: fp32 rows [B*H*W][ld] (channels 0..2 of conv_out) -> uint8 RGB, every step a separately rounded fp32 op
+// (the library builds with -ffp-contract=off):
+//   mode 0 (torchvision make_grid(normalize=True, value_range=(lo, hi)) + save_image):
+//          v = (min(max(x, lo), hi) - lo) / (hi - lo);  u = trunc(min(max(v * 255 + 0.5, 0), 255))  (v * 255, then + 0.5)
+//   mode 1 (diffusers / SD generate-images.py):  v = min(max(x / 2 + 0.5, 0), 1);  u = rint(v * 255)  (half to even)
+// The rows hold samples b0 .. b0+B-1 of a batch of n.  nrow == 0: out = [n][H][W][3], this launch writes its B samples.  nrow > 0: out =
+// the make_grid canvas [Hc][Wc][3] (xmaps = min(nrow, n) columns, cells (H+p) x (W+p) behind a p-pixel border, n == 1: the bare image);
+// one thread per canvas pixel, each launch writes the pixels of its own samples and the launch with b0 == 0 also the pad pixels (byte 0).
+__device__ __forceinline__ uint8_t img_u8(float x, int mode, float lo, float hi) {
+  if (mode == 0) {
+    const float c = fminf(fmaxf(x, lo), hi);
+    const float v = (c - lo) / (hi - lo);
+    float t = v * 255.0f;
+    t = t + 0.5f;
+    t = fminf(fmaxf(t, 0.0f), 255.0f);
+    return (uint8_t)(int)t;
+  }
+  float v = x / 2.0f + 0.5f;
+  v = fminf(fmaxf(v, 0.0f), 1.0f);
+  return (uint8_t)(int)rintf(v * 255.0f);
+}
+__global__ __launch_bounds__(TPB) void k_rows_to_image_u8(const float* __restrict__ rows, int ld, int B, int H, int W, int mode, float lo,
+                                                          float hi, int xmaps, int pad, int Hc, int Wc, int b0, int n,
+                                                          uint8_t* __restrict__ out) {
+  const int64_t npx = (int64_t)Hc * Wc;
+  const int ch = H + pad, cw = W + pad;
+  for (int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x; q < npx; q += (int64_t)gridDim.x * TPB) {
+    int k, iy, ix;
+    if (xmaps == 0) {                                 // [n][H][W][3]: canvas = the B samples of this launch, one after the other
+      k = b0 + (int)(q / ((int64_t)H * W));
+      const int r = (int)(q % ((int64_t)H * W));
+      iy = r / W; ix = r - iy * W;
+    } else {
+      const int y = (int)(q / Wc) - pad, x = (int)(q % Wc) - pad;
+      bool img = y >= 0 && x >= 0;
+      k = -1; iy = ix = 0;
+      if (img) {
+        const int cy = y / ch, cx = x / cw;
+        iy = y - cy * ch; ix = x - cx * cw;
+        k = cy * xmaps + cx;
+        img = iy < H && ix < W && cx < xmaps && k < n;
+      }
+      if (!img) {
+        if (b0 == 0) { uint8_t* o = out + q * 3; o[0] = 0; o[1] = 0; o[2] = 0; }
+        continue;
+      }
+      if (k < b0 || k >= b0 + B) continue;
+    }
+    const float* px = rows + ((int64_t)(k - b0) * H * W + (int64_t)iy * W + ix) * ld;
+    const int64_t at = xmaps == 0 ? ((int64_t)k * H * W + (int64_t)iy * W + ix) * 3 : q * 3;
+    out[at + 0] = img_u8(px[0], mode, lo, hi);
+    out[at + 1] = img_u8(px[1], mode, lo, hi);
+    out[at + 2] = img_u8(px[2], mode, lo, hi);
+  }
+}
 __global__ __launch_bounds__(TPB) void k_rows_to_nchw(const float* __restrict__ rows, int ld, int B, int C, int HW, float* __restrict__ x) {
   const int64_t n = (int64_t)B * C * HW;
   for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
@@ -2505,6 +2560,28 @@ int sfron_image_u8_to_rows_bf16(const uint8_t* img, int B, int H, int W, const u
 int sfron_nchw_to_rows_f32(const float* x, int B, int C, int HW, int ld, float* rows, void* stream) {
   SFRON_CHECK_ARG(x && rows && ld >= C);
   hipLaunchKernelGGL(k_nchw_to_rows_f32, dim3(grid_for((int64_t)B * HW * ld)), dim3(TPB), 0, (hipStream_t)stream, x, B, C, HW, ld, rows);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int mode, float lo, float hi, int nrow, int padding, int b0, int n,
+                           uint8_t* out, void* stream) {
+  SFRON_CHECK_ARG(rows && out && ld >= 3 && B > 0 && H > 0 && W > 0 && (mode == SFRON_IMAGE_SAVE_IMAGE || mode == SFRON_IMAGE_ROUND));
+  SFRON_CHECK_ARG(nrow >= 0 && padding >= 0 && b0 >= 0 && n >= b0 + B && (mode != SFRON_IMAGE_SAVE_IMAGE || hi > lo));
+  int xmaps = 0, pad = 0;
+  int64_t Hc, Wc;
+  if (nrow > 0 && n > 1) {                      // make_grid: n == 1 returns the image itself
+    xmaps = nrow < n ? nrow : n;
+    const int ymaps = (n + xmaps - 1) / xmaps;
+    pad = padding;
+    Hc = (int64_t)ymaps * (H + pad) + pad; Wc = (int64_t)xmaps * (W + pad) + pad;
+  } else if (nrow > 0) {
+    xmaps = 1; Hc = H; Wc = W;                  // one cell, no border (b0 == 0, B == 1)
+  } else {
+    Hc = (int64_t)B * H; Wc = W;                // the B samples of this launch
+  }
+  SFRON_CHECK_ARG(Hc * Wc * 3 < (1ll << 31) && Hc < (1 << 30) && Wc < (1 << 30));
+  hipLaunchKernelGGL(k_rows_to_image_u8, dim3(grid_for(Hc * Wc)), dim3(TPB), 0, (hipStream_t)stream, rows, ld, B, H, W, mode, lo, hi, xmaps,
+                     pad, (int)Hc, (int)Wc, b0, n, out);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

@@ -197,6 +197,43 @@ __global__ __launch_bounds__(TPB) void k_vae_moments(const float* __restrict__ r
   }
 }
 
+// The VAE decoder's head: post_quant_conv(z / scale) from the NCHW fp32 latents [B][zc][hw] to the rows conv_in reads, one thread per
+// pixel.  x[c] = z / scale (a correctly rounded division), then acc = bias[o]; acc = acc + w[o][c] * x[c] for c ascending, a separate
+// multiply and add each (no contraction).  bf16 rows [B*hw][Cp] (RNE, channels zc.. zero, 16-byte stores) and optionally the same values
+// as fp32 before the rounding.
+__global__ __launch_bounds__(TPB) void k_vae_latent_in(const float* __restrict__ z, int B, int zc, int hw, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, float scale, int Cp, __bf16* __restrict__ rows,
+                                                       float* __restrict__ rows_f32) {
+  const int64_t n = (int64_t)B * hw;
+  for (int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x; p < n; p += (int64_t)gridDim.x * TPB) {
+    const int64_t b = p / hw, r = p - b * hw;
+    float x[16], y[16];
+    for (int c = 0; c < zc; ++c) x[c] = z[(b * zc + c) * hw + r] / scale;
+    for (int o = 0; o < zc; ++o) {
+      float acc = bias[o];
+      for (int c = 0; c < zc; ++c) {
+        const float t = w[o * zc + c] * x[c];
+        acc = acc + t;
+      }
+      y[o] = acc;
+    }
+    for (int g = 0; g < Cp / 8; ++g) {
+      bf16x8 v;
+      for (int j = 0; j < 8; ++j) v[j] = 8 * g + j < zc ? f2bf(y[8 * g + j]) : (__bf16)0.0f;
+      reinterpret_cast<bf16x8*>(rows + p * Cp)[g] = v;
+      if (rows_f32) {
+        float4* o4 = reinterpret_cast<float4*>(rows_f32 + p * Cp) + 2 * g;
+        float4 a, c;
+        a.x = 8 * g + 0 < zc ? y[8 * g + 0] : 0.0f; a.y = 8 * g + 1 < zc ? y[8 * g + 1] : 0.0f;
+        a.z = 8 * g + 2 < zc ? y[8 * g + 2] : 0.0f; a.w = 8 * g + 3 < zc ? y[8 * g + 3] : 0.0f;
+        c.x = 8 * g + 4 < zc ? y[8 * g + 4] : 0.0f; c.y = 8 * g + 5 < zc ? y[8 * g + 5] : 0.0f;
+        c.z = 8 * g + 6 < zc ? y[8 * g + 6] : 0.0f; c.w = 8 * g + 7 < zc ? y[8 * g + 7] : 0.0f;
+        o4[0] = a; o4[1] = c;
+      }
+    }
+  }
+}
+
 inline int grid_for(int64_t n) {
   int64_t b = (n + TPB - 1) / TPB;
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -267,6 +304,16 @@ int sfron_vae_moments(const float* rows, int ld, int B, int hw, int z2, const fl
   SFRON_CHECK_ARG((moments_f32 || moments_f16 || latent) && (latent == nullptr) == (eps == nullptr));
   hipLaunchKernelGGL(k_vae_moments, dim3(grid_for((int64_t)B * hw)), dim3(TPB), 0, (hipStream_t)stream, rows, ld, B, hw, z2, w, bias, moments_f32,
                      (_Float16*)moments_f16, eps, scale, latent);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_vae_latent_in(const float* z, int B, int zc, int hw, const float* w, const float* bias, float scale, int c_pad, uint16_t* rows,
+                        float* rows_f32, void* stream) {
+  SFRON_CHECK_ARG(z && w && bias && rows && B > 0 && hw > 0 && zc > 0 && zc <= 16 && c_pad >= zc && c_pad % 8 == 0);
+  SFRON_CHECK_ARG(((uintptr_t)rows & 15) == 0 && ((uintptr_t)rows_f32 & 15) == 0);
+  hipLaunchKernelGGL(k_vae_latent_in, dim3(grid_for((int64_t)B * hw)), dim3(TPB), 0, (hipStream_t)stream, z, B, zc, hw, w, bias, scale, c_pad,
+                     (__bf16*)rows, rows_f32);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

@@ -50,9 +50,13 @@ class LatentDiffusion:
 
     parameterization, first_stage_key, cond_stage_key = "eps", "jpg", "txt"
 
-    def __init__(self, unet, schedule=None):
+    scale_factor = 0.18215
+
+    def __init__(self, unet, schedule=None, first_stage_decoder=None):
+        """first_stage_decoder: a vae.VAEDecoder; with it ``decode_first_stage(z)`` decodes latents (ldm's 1 / scale_factor * z)."""
         import types
         self.model = types.SimpleNamespace(diffusion_model=unet, conditioning_key="crossattn")
+        self.first_stage_decoder = first_stage_decoder
         self.schedule = schedule or LDMSchedule(device=unet.device_)
         self.num_timesteps = self.schedule.num_timesteps
         self.training = True
@@ -84,7 +88,14 @@ class LatentDiffusion:
     def _outside(self, *a, **k):
         raise NotImplementedError("the VAE / CLIP front-end of LatentDiffusion is outside the unlearning hot path: hand latents and prompt "
                                   "embeddings in (sfron.latents for cached VAE moments)")
-    get_input = shared_step = encode_first_stage = decode_first_stage = get_learned_conditioning = _outside
+    get_input = shared_step = encode_first_stage = get_learned_conditioning = _outside
+
+    def decode_first_stage(self, z, *a, **k):
+        """ddpm.py decode_first_stage: first_stage_model.decode(1 / scale_factor * z) -> fp32 [B, 3, H, W] in about [-1, 1], through the
+        attached VAEDecoder (z / scale_factor in its head kernel); without one it raises as the rest of the front end does."""
+        if self.first_stage_decoder is None:
+            return self._outside(z, *a, **k)
+        return self.first_stage_decoder.decode(z, scale=self.scale_factor)
 
 
 class SDSFRon:

@@ -7,10 +7,16 @@ Restates SD/ldm/modules/diffusionmodules/model.py ``Encoder`` (conv_in, per leve
 step.  No tape, no autograd: activations are NHWC fp32 rows between blocks and bf16 where they feed a product, in a few ping-pong
 workspaces reused across calls, on the current stream.
 
+The decoder (``VAEDecoder``) is the other direction on the same blocks: ``post_quant_conv(z / scale)`` (one launch of
+sfron_vae_latent_in), the ldm ``Decoder`` (conv_in, mid ResnetBlock / AttnBlock / ResnetBlock, per level from the top down
+``num_res_blocks + 1`` ResnetBlocks [+ AttnBlocks] and a nearest x2 Upsample + 3x3 conv on every level but 0, GroupNorm + swish +
+conv_out), then fp32 NCHW images or the uint8 bytes of save_image / diffusers (sfron_rows_to_image_u8, optionally as the make_grid canvas)
+-- what DiT/forget.py:114-145 and SD/eval-scripts/generate-images.py:181-192 run through ``vae.decode``.
+
 Chunk invariant: the products take their operands through buffer resources sized by a 32-bit byte count (k_cgemm, conv.hip) and an
 ``int`` row count, so an operand of 2 GiB or more is read WRONG, silently.  A batch is therefore run in chunks of samples whose largest
-operand stays under ``max_chunk_bytes`` (default 1 GiB: 32 images at 256 px, 8 at 512 px), and every launch asserts its operands are
-below 2 GiB.
+operand stays under ``max_chunk_bytes`` (default 1 GiB: 32 images at 256 px, 8 at 512 px for the encoder; 16 and 4 for the decoder,
+whose largest operand is the 256-channel level after the last upsample), and every launch asserts its operands are below 2 GiB.
 """
 import ctypes
 import json
@@ -196,6 +202,166 @@ def canonical_state_dict(sd, specs=None):
     return out
 
 
+def decoder_plan(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3, attn_resolutions=(), resolution=256):
+    """(parameter specs in Decoder.named_parameters() order + post_quant_conv, op list in execution order) of the reference Decoder
+    (model.py:496-626) and AutoencoderKL's post_quant_conv (autoencoder.py:385-389).  The up levels run from the top down but are
+    registered from level 0 up (``self.up.insert(0, up)``).  Ops: ("conv_in", zc, c), ("res", name, cin, cout), ("attn", name, c),
+    ("up", name, c) (nearest x2 + 3x3 conv, model.py:44-57), ("out", c)."""
+    P, ops = [], []
+
+    def conv(dst, name, o, i, k):
+        dst.extend([(name + ".weight", (o, i, k, k)), (name + ".bias", (o,))])
+
+    def gn(dst, name, c):
+        dst.extend([(name + ".weight", (c,)), (name + ".bias", (c,))])
+
+    def res(dst, name, cin, cout):
+        gn(dst, name + ".norm1", cin); conv(dst, name + ".conv1", cout, cin, 3); gn(dst, name + ".norm2", cout)
+        conv(dst, name + ".conv2", cout, cout, 3)
+        if cin != cout:
+            conv(dst, name + ".nin_shortcut", cout, cin, 1)
+        ops.append(("res", name, cin, cout))
+
+    def attn(dst, name, c):
+        gn(dst, name + ".norm", c)
+        for w in ("q", "k", "v", "proj_out"):
+            conv(dst, name + "." + w, c, c, 1)
+
+    nl = len(ch_mult)
+    block_in = ch * ch_mult[nl - 1]
+    cur = resolution // 2 ** (nl - 1)
+    conv(P, "conv_in", block_in, z_channels, 3)
+    ops.append(("conv_in", z_channels, block_in))
+    res(P, "mid.block_1", block_in, block_in)
+    attn(P, "mid.attn_1", block_in)
+    ops.append(("attn", "mid.attn_1", block_in))
+    res(P, "mid.block_2", block_in, block_in)
+    levels = {}
+    for lvl in reversed(range(nl)):
+        L, attns = [], []
+        block_out = ch * ch_mult[lvl]
+        for ib in range(num_res_blocks + 1):
+            res(L, f"up.{lvl}.block.{ib}", block_in, block_out)
+            block_in = block_out
+            if cur in attn_resolutions:
+                attns.append(f"up.{lvl}.attn.{ib}")
+                ops.append(("attn", attns[-1], block_in))
+        for a in attns:                              # the attn ModuleList is registered after the block ModuleList
+            attn(L, a, block_in)
+        if lvl != 0:
+            conv(L, f"up.{lvl}.upsample.conv", block_in, block_in, 3)
+            ops.append(("up", f"up.{lvl}.upsample.conv", block_in))
+            cur *= 2
+        levels[lvl] = L
+    for lvl in range(nl):                            # registration order: up.0 first
+        P.extend(levels[lvl])
+    gn(P, "norm_out", block_in)
+    conv(P, "conv_out", out_ch, block_in, 3)
+    ops.append(("out", block_in))
+    conv(P, "post_quant_conv", z_channels, z_channels, 1)
+    return OrderedDict(P), ops
+
+
+def _levels(specs):
+    return 1 + max(int(n.split(".")[1]) for n in specs if n.startswith("up."))
+
+
+def _diffusers_decoder_name(name, levels, new_attn):
+    """ldm Decoder name (no prefix) -> diffusers AutoencoderKL name (decoder. prefix); diffusers numbers the up blocks from the top:
+    up_blocks.j is ldm up.{levels-1-j}."""
+    if name.startswith("post_quant_conv."):
+        return name
+    parts = name.split(".")
+    if parts[0] == "norm_out":
+        return "decoder.conv_norm_out." + parts[1]
+    if parts[0] in ("conv_in", "conv_out"):
+        return "decoder." + name
+    if parts[0] == "up":
+        j, kind = levels - 1 - int(parts[1]), parts[2]
+        if kind == "block":
+            sub = parts[4].replace("nin_shortcut", "conv_shortcut")
+            return f"decoder.up_blocks.{j}.resnets.{parts[3]}.{sub}.{parts[5]}"
+        if kind == "upsample":
+            return f"decoder.up_blocks.{j}.upsamplers.0.conv.{parts[4]}"
+        if kind == "attn":
+            m = _ATTN_DIFFUSERS_NEW if new_attn else _ATTN_DIFFUSERS
+            return f"decoder.up_blocks.{j}.attentions.{parts[3]}.{m[parts[4]]}.{parts[5]}"
+    if parts[0] == "mid":
+        return "decoder." + _diffusers_name(name, new_attn)[len("encoder."):]
+    raise KeyError(name)
+
+
+def diffusers_decoder_key_map(specs, new_attn=False):
+    """{ldm name: diffusers name} for every canonical decoder key (the decoder half of convertModels.py:594
+    convert_ldm_vae_checkpoint)."""
+    nl = _levels(specs)
+    return OrderedDict((n, _diffusers_decoder_name(n, nl, new_attn)) for n in specs)
+
+
+def _ldm_decoder_name(key, levels):
+    """diffusers AutoencoderKL name -> ldm Decoder name (None for keys outside the decoder: encoder, quant_conv)."""
+    if key.startswith("post_quant_conv."):
+        return key
+    if not key.startswith("decoder."):
+        return None
+    p = key[len("decoder."):].split(".")
+    if p[0] == "conv_norm_out":
+        return "norm_out." + p[1]
+    if p[0] in ("conv_in", "conv_out"):
+        return ".".join(p)
+    if p[0] == "up_blocks":
+        lvl = levels - 1 - int(p[1])
+        if p[2] == "resnets":
+            return f"up.{lvl}.block.{p[3]}.{p[4].replace('conv_shortcut', 'nin_shortcut')}.{p[5]}"
+        if p[2] == "upsamplers":
+            return f"up.{lvl}.upsample.conv.{p[5]}"
+        if p[2] == "attentions":
+            return f"up.{lvl}.attn.{p[3]}.{_ATTN_LDM['.'.join(p[4:-1])]}.{p[-1]}"
+    if p[0] == "mid_block":
+        return _ldm_name("encoder." + ".".join(p))
+    raise KeyError(f"unknown diffusers VAE decoder key {key!r}")
+
+
+def canonical_decoder_state_dict(sd, specs=None):
+    """Any supported VAE state dict -> {ldm Decoder name (no prefix) | post_quant_conv.*: fp32 CPU tensor}, shaped as the ldm modules.
+    The formats of ``canonical_state_dict`` (ldm AutoencoderKL decoder.* + post_quant_conv.*, CompVis first_stage_model.*, diffusers with
+    either attention naming; Linear [C, C] attention weights become 1x1 convolutions).  Encoder keys are ignored.  ``specs``
+    (decoder_plan's) checks names and shapes: an incomplete or unknown key set raises and names the keys."""
+    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
+        sd = sd["state_dict"]
+    if any(k.startswith("first_stage_model.") for k in sd):
+        sd = {k[len("first_stage_model."):]: v for k, v in sd.items() if k.startswith("first_stage_model.")}
+    diffusers = any(k.startswith(("decoder.up_blocks.", "decoder.mid_block.", "decoder.conv_norm_out.")) for k in sd)
+    if diffusers:
+        levels = _levels(specs) if specs is not None else \
+            1 + max([int(k.split(".")[2]) for k in sd if k.startswith("decoder.up_blocks.")] or [0])
+    out = OrderedDict()
+    for k, v in sd.items():
+        if diffusers:
+            n = _ldm_decoder_name(k, levels)
+        else:
+            n = k[len("decoder."):] if k.startswith("decoder.") else (k if k.startswith("post_quant_conv.") else None)
+        if n is None:
+            continue
+        t = torch.as_tensor(v).detach().to("cpu", torch.float32)
+        if t.dim() == 2 and ".attn" in n and n.endswith(".weight"):          # diffusers Linear -> 1x1 conv
+            t = t.reshape(t.shape[0], t.shape[1], 1, 1)
+        out[n] = t
+    if not out:
+        raise KeyError(f"not a VAE state dict: no decoder.* / post_quant_conv.* / first_stage_model.* keys (first keys: {list(sd)[:5]})")
+    if specs is not None:
+        missing = [n for n in specs if n not in out]
+        extra = [n for n in out if n not in specs]
+        if missing or extra:
+            raise KeyError(f"VAE decoder state dict does not match the configuration: missing {missing[:8]}"
+                           f"{' ...' if len(missing) > 8 else ''}, unexpected {extra[:8]}")
+        for n, shp in specs.items():
+            if tuple(out[n].shape) != tuple(shp):
+                raise ValueError(f"{n}: shape {tuple(out[n].shape)}, the configuration needs {tuple(shp)}")
+        out = OrderedDict((n, out[n]) for n in specs)
+    return out
+
+
 def load_state_file(path):
     """A diffusers directory (config.json + diffusion_pytorch_model.safetensors | .bin) or one .ckpt / .pt / .bin / .safetensors file ->
     (state dict, config dict or None)."""
@@ -216,21 +382,13 @@ def load_state_file(path):
 
 
 # ------------------------------------------------------------------------------------------------ the encoder
-class VAEEncoder:
-    """image -> VAE posterior moments / latent on the GPU.  ``moments(images)`` gives [B, 2z, H/8, W/8] fp32 (mean || logvar);
-    ``encode(images)`` the scaled posterior sample.  images: uint8 [B, H, W, 3] (host or device; ``flip`` uint8/bool [B] mirrors a
-    sample) or fp32 [B, 3, H, W] in [-1, 1]."""
+class _VAENet:
+    """What the encoder and the decoder share: the weight arena (fp32 + bf16 copy, conv_wprep operands), the grown-never-shrunk
+    workspaces and the forward blocks over the HIP kernels.  A subclass sets ``specs`` / ``ops`` and calls ``_arena``."""
 
-    def __init__(self, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, in_channels=3, attn_resolutions=(), device="cuda",
-                 max_chunk_bytes=1 << 30, resolution=256):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.SfronError("VAEEncoder needs a GPU (no CPU fallback)")
-        if ch % 32:
-            raise ValueError("GroupNorm(32) needs ch % 32 == 0")
-        self.ch, self.ch_mult, self.z, self.in_channels = ch, tuple(ch_mult), z_channels, in_channels
-        self.max_chunk_bytes = int(max_chunk_bytes)
-        self.specs, self.ops = encoder_plan(ch, ch_mult, num_res_blocks, z_channels, in_channels, attn_resolutions, resolution)
+    _CONFIG_KEYS = (("layers_per_block", "num_res_blocks"), ("latent_channels", "z_channels"))
+
+    def _arena(self):
         # arena: q / k / v of each attention as one [3C][C] matrix + [3C] bias, everything else in order; tensors at multiples of 8
         groups = []
         for op in self.ops:
@@ -264,18 +422,23 @@ class VAEEncoder:
         return m
 
     @classmethod
-    def from_pretrained(cls, path, **kw):
-        """A diffusers AutoencoderKL directory or a single .ckpt / .pt / .safetensors (ldm, CompVis or diffusers keys)."""
-        sd, cfg = load_state_file(path)
+    def _config_kwargs(cls, cfg, kw):
+        """diffusers config.json -> constructor keywords (explicit keywords win)."""
         if cfg is not None:
             bo = cfg.get("block_out_channels")
             if bo:
                 kw.setdefault("ch", bo[0])
                 kw.setdefault("ch_mult", tuple(b // bo[0] for b in bo))
-            for src, dst in (("layers_per_block", "num_res_blocks"), ("latent_channels", "z_channels"), ("in_channels", "in_channels")):
+            for src, dst in cls._CONFIG_KEYS:
                 if src in cfg:
                     kw.setdefault(dst, cfg[src])
-        return cls.from_state_dict(sd, **kw)
+        return kw
+
+    @classmethod
+    def from_pretrained(cls, path, **kw):
+        """A diffusers AutoencoderKL directory or a single .ckpt / .pt / .safetensors (ldm, CompVis or diffusers keys)."""
+        sd, cfg = load_state_file(path)
+        return cls.from_state_dict(sd, **cls._config_kwargs(cfg, kw))
 
     def state_dict(self):
         return OrderedDict((n, self.view(n).detach().cpu().clone()) for n in self.specs)
@@ -285,7 +448,7 @@ class VAEEncoder:
         return self.params[self.index[name]:self.index[name] + n].view(self.specs[name])
 
     def load_state_dict(self, sd):
-        can = canonical_state_dict(sd, self.specs)
+        can = self._canonical(sd)
         with torch.no_grad():
             for n, v in can.items():
                 self.view(n).copy_(v.to(self.dev))
@@ -313,27 +476,6 @@ class VAEEncoder:
             self._ws[key] = t = torch.empty(numel, dtype=dtype, device=self.dev)
         return t[:numel]
 
-    def per_sample_bytes(self, H, W):
-        """Bytes of the largest operand one sample contributes to a launch (fp32 activations; attention scores; the input)."""
-        big, res_h, res_w = max(H * W * 8 * 2, H * W * 3), H, W
-        for op in self.ops:
-            if op[0] == "conv_in":
-                big = max(big, res_h * res_w * self.ch * 4)
-            elif op[0] == "res":
-                big = max(big, res_h * res_w * max(op[2], op[3]) * 4)
-            elif op[0] == "attn":
-                T = res_h * res_w
-                big = max(big, T * T * 4, T * 3 * op[2] * 2, T * op[2] * 4)
-            elif op[0] == "down":
-                res_h, res_w = res_h // 2, res_w // 2
-        return big
-
-    def chunk_size(self, H, W):
-        ps = self.per_sample_bytes(H, W)
-        if ps >= _LIMIT:
-            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB (tiled encoding is not supported)")
-        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
-
     # ---------------------------------------------------------------- blocks (forward only)
     def _gn(self, x, B, HW, C, name, swish, out_key):
         y = self._buf(out_key, B * HW * C, torch.bfloat16)
@@ -345,13 +487,13 @@ class VAEEncoder:
                                        ptr(y), ptr(mean), ptr(rstd), ptr(ws), stream_ptr()), "groupnorm_fwd")
         return y
 
-    def _conv3(self, src, B, hs, ws, name, ho, wo, out_key, stride=1, pad=1, resid=None):
+    def _conv3(self, src, B, hs, ws, name, ho, wo, out_key, stride=1, pad=1, resid=None, up=0):
         v = self.conv3[name]
         out = self._buf(out_key, B * ho * wo * v["cop"], torch.float32).view(B * ho * wo, v["cop"])
         bias = self._zero_bias.get(name)
         bias = self._p(name + ".bias") if bias is None else bias
         _guard(src, out, resid)
-        d = _conv_desc(B, hs, ws, v["cip"], ho, wo, v["cop"], 9, stride, pad, 0, 0, bias=bias, resid=resid, out_f32=out, ld_out=v["cop"])
+        d = _conv_desc(B, hs, ws, v["cip"], ho, wo, v["cop"], 9, stride, pad, up, 0, bias=bias, resid=resid, out_f32=out, ld_out=v["cop"])
         check(_L().sfron_conv_fwd(ctypes.byref(d), ptr(src), ptr(v["fwd"]), stream_ptr()), "conv_fwd")
         return out
 
@@ -396,6 +538,51 @@ class VAEEncoder:
         _guard(O, out, x)
         bgemm(O, self._w(name + ".proj_out.weight"), rows, C, C, lda=C, ldb=C, bias=self._p(name + ".proj_out.bias"), c_f32=out, ldc=C, resid=x)
         return out
+
+
+
+class VAEEncoder(_VAENet):
+    """image -> VAE posterior moments / latent on the GPU.  ``moments(images)`` gives [B, 2z, H/8, W/8] fp32 (mean || logvar);
+    ``encode(images)`` the scaled posterior sample.  images: uint8 [B, H, W, 3] (host or device; ``flip`` uint8/bool [B] mirrors a
+    sample) or fp32 [B, 3, H, W] in [-1, 1]."""
+
+    _CONFIG_KEYS = _VAENet._CONFIG_KEYS + (("in_channels", "in_channels"),)
+
+    def __init__(self, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, in_channels=3, attn_resolutions=(), device="cuda",
+                 max_chunk_bytes=1 << 30, resolution=256):
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise _lib.SfronError("VAEEncoder needs a GPU (no CPU fallback)")
+        if ch % 32:
+            raise ValueError("GroupNorm(32) needs ch % 32 == 0")
+        self.ch, self.ch_mult, self.z, self.in_channels = ch, tuple(ch_mult), z_channels, in_channels
+        self.max_chunk_bytes = int(max_chunk_bytes)
+        self.specs, self.ops = encoder_plan(ch, ch_mult, num_res_blocks, z_channels, in_channels, attn_resolutions, resolution)
+        self._arena()
+
+    def _canonical(self, sd):
+        return canonical_state_dict(sd, self.specs)
+
+    def per_sample_bytes(self, H, W):
+        """Bytes of the largest operand one sample contributes to a launch (fp32 activations; attention scores; the input)."""
+        big, res_h, res_w = max(H * W * 8 * 2, H * W * 3), H, W
+        for op in self.ops:
+            if op[0] == "conv_in":
+                big = max(big, res_h * res_w * self.ch * 4)
+            elif op[0] == "res":
+                big = max(big, res_h * res_w * max(op[2], op[3]) * 4)
+            elif op[0] == "attn":
+                T = res_h * res_w
+                big = max(big, T * T * 4, T * 3 * op[2] * 2, T * op[2] * 4)
+            elif op[0] == "down":
+                res_h, res_w = res_h // 2, res_w // 2
+        return big
+
+    def chunk_size(self, H, W):
+        ps = self.per_sample_bytes(H, W)
+        if ps >= _LIMIT:
+            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB (tiled encoding is not supported)")
+        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
 
     def _chunk(self, images, flip, lo, hi, mom_f32, mom_f16, eps, scale, lat):
         """Encoder + quant_conv (+ posterior sample) of samples [lo, hi) of the batch, results written at their batch offset."""
@@ -512,4 +699,167 @@ def encoder_flops(H, W, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channe
             total += 2.0 * h * w * op[2] * op[2] * 9
         elif op[0] == "out":
             total += 2.0 * h * w * 2 * z_channels * op[1] * 9 + 2.0 * h * w * (2 * z_channels) ** 2
+    return total
+
+
+# ------------------------------------------------------------------------------------------------ the decoder
+class VAEDecoder(_VAENet):
+    """latent -> image on the GPU: post_quant_conv(z / scale) + the ldm Decoder, forward only.  ``decode(z)`` gives fp32 [B, 3, H, W]
+    (``vae.decode(z / 0.18215).sample``); ``decode_u8`` the uint8 bytes a PNG holds, per image or as the make_grid canvas."""
+
+    _CONFIG_KEYS = _VAENet._CONFIG_KEYS + (("out_channels", "out_ch"),)
+
+    def __init__(self, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3, attn_resolutions=(), device="cuda",
+                 max_chunk_bytes=1 << 30, resolution=256):
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise _lib.SfronError("VAEDecoder needs a GPU (no CPU fallback)")
+        if ch % 32:
+            raise ValueError("GroupNorm(32) needs ch % 32 == 0")
+        if z_channels > 16:
+            raise ValueError("sfron_vae_latent_in takes at most 16 latent channels")
+        self.ch, self.ch_mult, self.z, self.out_ch = ch, tuple(ch_mult), z_channels, out_ch
+        self.max_chunk_bytes = int(max_chunk_bytes)
+        self.specs, self.ops = decoder_plan(ch, ch_mult, num_res_blocks, z_channels, out_ch, attn_resolutions, resolution)
+        self.factor = 1 << (len(self.ch_mult) - 1)
+        self._arena()
+
+    def _canonical(self, sd):
+        return canonical_decoder_state_dict(sd, self.specs)
+
+    def per_sample_bytes(self, H, W):
+        """Bytes of the largest operand one sample contributes to a launch, for an H x W output image (fp32 activations, the upsampled
+        convolution outputs, attention scores, the conv_out rows)."""
+        h, w = H // self.factor, W // self.factor
+        big = max(h * w * self.z * 4, h * w * _pad8(self.z) * 2, H * W * _pad8(self.out_ch) * 4)
+        for op in self.ops:
+            if op[0] == "conv_in":
+                big = max(big, h * w * op[2] * 4)
+            elif op[0] == "res":
+                big = max(big, h * w * max(op[2], op[3]) * 4)
+            elif op[0] == "attn":
+                T = h * w
+                big = max(big, T * T * 4, T * 3 * op[2] * 2, T * op[2] * 4)
+            elif op[0] == "up":
+                h, w = 2 * h, 2 * w
+                big = max(big, h * w * op[2] * 4)
+        return big
+
+    def chunk_size(self, H, W):
+        ps = self.per_sample_bytes(H, W)
+        if ps >= _LIMIT:
+            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB (tiled decoding is not supported)")
+        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
+
+    def _chunk(self, z, lo, hi, scale):
+        """post_quant_conv + Decoder of samples [lo, hi): returns the conv_out rows [B*H*W][8] fp32 (a workspace view)."""
+        L, B = _L(), hi - lo
+        h, w = z.shape[2], z.shape[3]
+        v = self.conv3["conv_in"]
+        zr = self._buf("bf_in", B * h * w * v["cip"], torch.bfloat16)
+        src = z[lo:hi]
+        _guard(src, zr)
+        check(L.sfron_vae_latent_in(ptr(src), B, self.z, h * w, self._p("post_quant_conv.weight"), self._p("post_quant_conv.bias"),
+                                    float(scale), v["cip"], ptr(zr), None, stream_ptr()), "vae_latent_in")
+        cur, spare = "f_x0", "f_x1"
+        x = self._conv3(zr, B, h, w, "conv_in", h, w, cur)
+        for op in self.ops[1:]:
+            if op[0] == "res":
+                x = self._resblock(x, B, h, w, op[1], op[2], op[3], spare)
+            elif op[0] == "attn":
+                x = self._attn(x, B, h, w, op[1], op[2], spare)
+            elif op[0] == "up":
+                xb = self._cast(x, B * h * w, op[2], "bf_b")
+                x = self._conv3(xb, B, h, w, op[1], 2 * h, 2 * w, spare, up=1)
+                h, w = 2 * h, 2 * w
+            elif op[0] == "out":
+                a = self._gn(x, B, h * w, op[1], "norm_out", True, "bf_a")
+                x = self._conv3(a, B, h, w, "conv_out", h, w, "f_h")
+                continue
+            cur, spare = spare, cur
+        return x
+
+    def _prepare(self, z):
+        z = torch.as_tensor(z)
+        if z.dim() != 4 or z.shape[1] != self.z:
+            raise ValueError(f"latents must be [B, {self.z}, h, w], got {tuple(z.shape)}")
+        z = z.to(self.dev, torch.float32).contiguous()
+        return z, z.shape[0], z.shape[2] * self.factor, z.shape[3] * self.factor
+
+    @torch.no_grad()
+    def decode(self, z, scale=0.18215):
+        """[B, out_ch, H, W] fp32 on the device: Decoder(post_quant_conv(z / scale)), H = h * 8 for KL-f8."""
+        z, B, H, W = self._prepare(z)
+        out = torch.empty(B, self.out_ch, H, W, dtype=torch.float32, device=self.dev)
+        n = self.chunk_size(H, W)
+        for lo in range(0, B, n):
+            hi = min(B, lo + n)
+            rows = self._chunk(z, lo, hi, scale)
+            dst = out[lo:hi]
+            _guard(rows, dst)
+            check(_L().sfron_rows_to_nchw(ptr(rows), rows.shape[1], hi - lo, self.out_ch, H * W, ptr(dst), stream_ptr()), "rows_to_nchw")
+        return out
+
+    @torch.no_grad()
+    def decode_u8(self, z, scale=0.18215, mode="save_image", nrow=0, padding=2, value_range=(-1.0, 1.0)):
+        """uint8 on the device.  mode "save_image": torchvision save_image(normalize=True, value_range) bytes; "round": the diffusers /
+        SD generate-images.py bytes ((x / 2 + 0.5).clamp(0, 1) * 255, rounded half to even).  nrow == 0: [B, H, W, 3]; nrow > 0: the
+        make_grid(nrow, padding) canvas [Hc, Wc, 3] (images.grid_geometry)."""
+        from .images import grid_geometry, image_mode
+        if self.out_ch != 3:
+            raise ValueError("decode_u8 writes RGB: out_ch must be 3")
+        m = image_mode(mode)
+        z, B, H, W = self._prepare(z)
+        lo_v, hi_v = (float(value_range[0]), float(value_range[1]))
+        if nrow > 0:
+            Hc, Wc = grid_geometry(B, H, W, nrow, padding)[:2]
+            out = torch.empty(Hc, Wc, 3, dtype=torch.uint8, device=self.dev)
+        else:
+            out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.dev)
+        n = self.chunk_size(H, W)
+        for lo in range(0, B, n):
+            hi = min(B, lo + n)
+            rows = self._chunk(z, lo, hi, scale)
+            _guard(rows, out)
+            check(_L().sfron_rows_to_image_u8(ptr(rows), rows.shape[1], hi - lo, H, W, m, lo_v, hi_v, int(nrow), int(padding), lo, B,
+                                               ptr(out), stream_ptr()), "rows_to_image_u8")
+        return out
+
+
+def load_autoencoder(src, **kw):
+    """(VAEEncoder, VAEDecoder) from ONE AutoencoderKL state: a path (read once, as from_pretrained) or a state dict in any supported
+    format.  Keywords common to both (ch, ch_mult, num_res_blocks, z_channels, attn_resolutions, resolution, device, max_chunk_bytes) go
+    to both; in_channels to the encoder, out_ch to the decoder."""
+    cfg = None
+    sd = src
+    if isinstance(src, (str, os.PathLike)):
+        sd, cfg = load_state_file(os.fspath(src))
+    enc_kw = {k: v for k, v in kw.items() if k != "out_ch"}
+    dec_kw = {k: v for k, v in kw.items() if k != "in_channels"}
+    enc = VAEEncoder.from_state_dict(sd, **VAEEncoder._config_kwargs(cfg, enc_kw))
+    dec = VAEDecoder.from_state_dict(sd, **VAEDecoder._config_kwargs(cfg, dec_kw))
+    return enc, dec
+
+
+def decoder_flops(H, W, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3, attn_resolutions=(), resolution=256):
+    """Algorithmic FLOPs of decoding one H x W image: 2 * pixels * Cout * Cin * k^2 per convolution (post_quant_conv included; an
+    Upsample's convolution at the doubled resolution) and 4 T^2 C per attention."""
+    specs, ops = decoder_plan(ch, ch_mult, num_res_blocks, z_channels, out_ch, attn_resolutions, resolution)
+    f = 1 << (len(ch_mult) - 1)
+    h, w = H // f, W // f
+    total = 2.0 * h * w * z_channels * z_channels
+    for op in ops:
+        if op[0] == "conv_in":
+            total += 2.0 * h * w * op[2] * op[1] * 9
+        elif op[0] == "res":
+            _, name, cin, cout = op
+            total += 2.0 * h * w * (cout * cin * 9 + cout * cout * 9 + (cout * cin if cin != cout else 0))
+        elif op[0] == "attn":
+            T, C = h * w, op[2]
+            total += 2.0 * T * C * 4 * C + 4.0 * T * T * C
+        elif op[0] == "up":
+            h, w = 2 * h, 2 * w
+            total += 2.0 * h * w * op[2] * op[2] * 9
+        elif op[0] == "out":
+            total += 2.0 * h * w * out_ch * op[1] * 9
     return total
