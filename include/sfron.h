@@ -185,7 +185,10 @@ enum {
    * pipelined tile: M % 256 == 0, N % 192 == 0, K % 128 == 0, ldc_bf16 % 8 == 0, ldaux % 8 == 0), otherwise SFRON_ERR_UNSUPPORTED; a forward
    * pass that wrote codes must be followed by the _Q dgrad (the two arrays are not interchangeable). */
   SFRON_EPI_GELU_Q = 7,   /* aux(u8) = code(gelu_tanh'(result)), c_bf16 = gelu_tanh(result)          -- Mlp.fc1+act */
-  SFRON_EPI_DGELU_Q = 8   /* c_bf16 = result * decode(aux(u8))                                 -- fc2 dgrad + act' */
+  SFRON_EPI_DGELU_Q = 8,  /* c_bf16 = result * decode(aux(u8))                                 -- fc2 dgrad + act' */
+  SFRON_EPI_QUICK_GELU = 9 /* c_bf16 = r * sigmoid(1.702 r), r = result + bias; no aux (forward only) -- CLIP text encoder fc1 + quick_gelu.
+                              Forward layout only (a_transposed = b_transposed = 0), no split, no accumulate; any M: the 128 x 128 tile where
+                              M % 128 == N % 128 == K % 64 == 0, the generic kernel otherwise */
 };
 typedef struct sfron_gemm_desc {
   const uint16_t* A; const uint16_t* B;
@@ -851,6 +854,22 @@ int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales
 int64_t sfron_dit_fp8_wgrad_workspace_bytes(const sfron_dit_cfg* cfg);
 int sfron_aux_set_fp8_wgrad(void* aux, void* workspace);
 int sfron_aux_destroy(void* aux);
+
+/* ------------------------------------------------------------------ CLIP text encoder (text.hip)
+ * SD v1's FrozenCLIPEmbedder (SD/ldm/modules/encoders/modules.py:230-266: CLIPTextModel(input_ids).last_hidden_state), forward only.  The
+ * residual stream is fp32 rows [B*T][D]; the per-layer LayerNorms are sfron_layernorm_fwd (bf16 out), q / k / v one sfron_gemm_bf16
+ * (SFRON_EPI_BF16) into [B*T][3D], out_proj and fc2 SFRON_EPI_F32 with bias and accumulate = 1 into the residual stream, fc1
+ * SFRON_EPI_QUICK_GELU. */
+/* out fp32 [B*T][D] = tok_emb[ids[b][t]] + pos_emb[t] (ids int64 [B][T], tok_emb fp32 [vocab][D], pos_emb fp32 [>= T][D]).  An id outside
+ * [0, vocab) is not read: its row is written as zeros and *err (a caller-owned device int, zeroed by the caller) gets bit 0 set. */
+int sfron_clip_embed(const int64_t* ids, int B, int T, const float* tok_emb, int vocab, const float* pos_emb, int D, float* out, int* err,
+                     void* stream);
+/* causal softmax(q k^T * hd^-0.5) v: qkv / o in the layout of sfron_attn_fwd (qkv bf16 [B*T][3*H*hd], column = which*D + head*hd + d;
+ * o bf16 [B*T][H*hd]); key j > query i is masked.  T <= 128 and hd == 64 only (else SFRON_ERR_UNSUPPORTED); one workgroup per (sample, head).
+ * qkv 16-byte, o 8-byte aligned.  Rows at or beyond T are neither read nor written. */
+int sfron_attn_causal_fwd(const uint16_t* qkv, uint16_t* o, int B, int T, int H, int hd, void* stream);
+/* y fp32 [rows][D] = LayerNorm(x; eps) * gamma + beta (the final LayerNorm: last_hidden_state is fp32) */
+int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, float* y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,7 @@ class GemmDesc(ctypes.Structure):
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_GATE_RES, EPI_DGELU, EPI_POS = range(6)
 EPI_GELU_Q, EPI_DGELU_Q = 7, 8          # round 6: GELU' as one byte per element (include/sfron.h)
+EPI_QUICK_GELU = 9                      # CLIP text encoder fc1: r * sigmoid(1.702 r), forward only
 
 _PROTOS["sfron_gemm_bf16"] = (c_int, [POINTER(GemmDesc), _S])
 _PROTOS["sfron_gemm_rowsum_supported"] = (c_int, [c_int, c_int, c_int])
@@ -285,6 +286,13 @@ _PROTOS.update({
     "sfron_probe_reset": (c_int, [c_void_p]),
     "sfron_probe_read": (c_int, [c_void_p, POINTER(c_int), POINTER(c_double)]),
     "sfron_probe_destroy": (c_int, [c_void_p]),
+})
+
+
+_PROTOS.update({
+    "sfron_clip_embed": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _S]),
+    "sfron_attn_causal_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _S]),
+    "sfron_layernorm_fwd_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, _P, _S]),
 })
 
 

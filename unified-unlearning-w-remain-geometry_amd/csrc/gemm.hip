@@ -67,7 +67,8 @@ constexpr int TILE_ELEMS = 128 * 64;   // both image kinds hold 8192 bf16 = 16 K
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_GATE_RES = 3, EPI_DGELU = 4, EPI_POS = 5, EPI_SUMSQ = 6,
        // round 6, the 256 x 192 pipelined tile only: EPI_GELU / EPI_DGELU whose `aux` is GELU'(pre-activation) as ONE byte per element
        // (common.h geluq_pack4) instead of the bf16 pre-activation: fc1 writes 113 instead of 151 MB, the fc2 dgrad reads half and has no exp
-       EPI_GELUQ = 7, EPI_DGELUQ = 8 };
+       EPI_GELUQ = 7, EPI_DGELUQ = 8,
+       EPI_QGELU = 9 };     // c_bf16 = quick_gelu(result) = r * sigmoid(1.702 r) (CLIP text encoder fc1; generic kernel and the 128 x 128 tile)
 
 
 
@@ -192,6 +193,11 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, int row, int c
     const bf16x4 h = *reinterpret_cast<const bf16x4*>(g.aux + (size_t)row * g.ldaux + col);
     const bf16x4 o = f2bf4(v * gelu_tanh_grad4(bf2f4(h)));
     *reinterpret_cast<bf16x4*>(g.Cb + (size_t)row * g.ldcb + col) = o;
+  } else if (EPI == EPI_QGELU) {
+    f32x4 q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = v[j] / (1.0f + __expf(-1.702f * v[j]));
+    *reinterpret_cast<bf16x4*>(g.Cb + (size_t)row * g.ldcb + col) = f2bf4(q);
   } else if (EPI == EPI_POS) {
     const float4 pe = *reinterpret_cast<const float4*>(g.pos + (size_t)(row % g.T) * g.N + col);
     *reinterpret_cast<float4*>(g.Cf + (size_t)row * g.ldcf + col) =
@@ -793,6 +799,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm_fast(GemmArgs g) {
   template __global__ void k_gemm_fast<WM, WN, MT, NT, true, true, 0>(GemmArgs);    \
   template __global__ void k_gemm_fast<WM, WN, MT, NT, true, true, 1>(GemmArgs);
 SFRON_INST_TILE(2, 2, 4, 4)
+template __global__ void k_gemm_fast<2, 2, 4, 4, false, false, EPI_QGELU>(GemmArgs);
 SFRON_INST_TILE(4, 2, 4, 6)
 SFRON_INST_TILE(2, 4, 8, 4)
 SFRON_INST_TILE(4, 2, 6, 6)
@@ -1996,6 +2003,11 @@ int sfron_gemm_bf16(const sfron_gemm_desc* d, void* stream) {
       SFRON_CHECK_ARG((((uintptr_t)g.aux | (uintptr_t)g.Cb) & 15) == 0);
       if (!sfron_gemm_gelu_q_supported(d->M, d->N, d->K)) return SFRON_ERR_UNSUPPORTED;
       return launch_pipe<4, 2, 4, 6, false, true, EPI_DGELUQ, 1>(g, s);
+    case SFRON_EPI_QUICK_GELU:
+      // CLIP fc1: M = prompts * 77 rows fills the 128 x 128 tile only for multiples of 128 prompts; every other shape runs on the generic kernel
+      SFRON_CHECK_ARG(g.Cb && g.ldcb % 4 == 0 && !d->a_transposed && !d->b_transposed && d->split_k <= 1 && !d->accumulate);
+      if ((force == 0 || force == 1) && d->K % 64 == 0 && tile_fits(g, 1)) return launch_fast<2, 2, 4, 4, false, false, EPI_QGELU>(g, s);
+      return launch<false, false, EPI_QGELU>(g, s);
     case SFRON_EPI_POS:
       SFRON_CHECK_ARG(g.Cf && g.pos && g.ldcf % 4 == 0 && !d->a_transposed && !d->b_transposed);
       if (force == 0 && shortk_ok(g)) return launch_shortk(g, s);          // the patch embedding: K = 16

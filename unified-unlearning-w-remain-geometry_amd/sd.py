@@ -45,18 +45,22 @@ class LatentDiffusion:
     ``apply_model(x_noisy, t, cond)`` (:1121-1131, crossattn conditioning: cond = the prompt embedding [B, 77, 768] or
     {"c_crossattn": [embedding]}), ``p_losses(x_start, cond, t, noise)`` -> (loss, loss_dict) (:1286-1319 with the v1-inference.yaml
     settings: eps-parameterisation, l2, logvar = 0 and not learned, l_simple_weight 1, original_elbo_weight 0).  The outputs take part
-    in torch autograd (gradients land in the UNet's flat arena).  The first stage (VAE) and the text encoder (get_input,
-    encode_first_stage, get_learned_conditioning, shared_step) are outside the path: latents and embeddings arrive resident."""
+    in torch autograd (gradients land in the UNet's flat arena).  The first stage (VAE) and the text encoder are outside the path:
+    latents and embeddings arrive resident.  get_input, encode_first_stage and shared_step raise; get_learned_conditioning and
+    decode_first_stage run through an attached text.CLIPTextEncoder / vae.VAEDecoder and raise without one."""
 
     parameterization, first_stage_key, cond_stage_key = "eps", "jpg", "txt"
 
     scale_factor = 0.18215
 
-    def __init__(self, unet, schedule=None, first_stage_decoder=None):
-        """first_stage_decoder: a vae.VAEDecoder; with it ``decode_first_stage(z)`` decodes latents (ldm's 1 / scale_factor * z)."""
+    def __init__(self, unet, schedule=None, first_stage_decoder=None, cond_stage_model=None):
+        """first_stage_decoder: a vae.VAEDecoder; with it ``decode_first_stage(z)`` decodes latents (ldm's 1 / scale_factor * z).
+        cond_stage_model: a text.CLIPTextEncoder (anything with ``encode(prompts)``); with it ``get_learned_conditioning(prompts)`` gives
+        the [B, 77, D] contexts."""
         import types
         self.model = types.SimpleNamespace(diffusion_model=unet, conditioning_key="crossattn")
         self.first_stage_decoder = first_stage_decoder
+        self.cond_stage_model = cond_stage_model
         self.schedule = schedule or LDMSchedule(device=unet.device_)
         self.num_timesteps = self.schedule.num_timesteps
         self.training = True
@@ -88,7 +92,14 @@ class LatentDiffusion:
     def _outside(self, *a, **k):
         raise NotImplementedError("the VAE / CLIP front-end of LatentDiffusion is outside the unlearning hot path: hand latents and prompt "
                                   "embeddings in (sfron.latents for cached VAE moments)")
-    get_input = shared_step = encode_first_stage = get_learned_conditioning = _outside
+    get_input = shared_step = encode_first_stage = _outside
+
+    def get_learned_conditioning(self, c):
+        """ddpm.py get_learned_conditioning with cond_stage_forward None: cond_stage_model.encode(c) (FrozenCLIPEmbedder: prompts ->
+        last_hidden_state) through the attached encoder; without one it raises as the rest of the front end does."""
+        if getattr(self, "cond_stage_model", None) is None:
+            return self._outside(c)
+        return self.cond_stage_model.encode(c)
 
     def decode_first_stage(self, z, *a, **k):
         """ddpm.py decode_first_stage: first_stage_model.decode(1 / scale_factor * z) -> fp32 [B, 3, H, W] in about [-1, 1], through the
