@@ -1,0 +1,490 @@
+"""The convolution, GroupNorm, batched-GEMM and softmax kernels of csrc/conv.hip at the shapes the KL-f8 VAE runs them at (vae.py): 256 and
+512 px images, 65 536 .. 262 144 pixels per sample, non-square crops, T = 1024 / 4096 single-head attention, operands just under 2 GiB --
+and the 2 GiB operand rule of the C entry points from both sides.
+
+Every reference is plain torch on the SAME bf16-rounded inputs, evaluated in fp64 on the GPU (a CPU reference of a 256 px convolution takes
+minutes); none calls the library.  The convolution reference is nine shifted matrix products over the padded NHWC image (no backend
+convolution algorithm in between, so integer inputs give exact integers).  Every comparison covers every element; the convolution cases
+additionally assert on the four image borders and on the last 256 output rows of the last sample on their own, so that a failure names its
+region.  Each check prints its largest error before it asserts (pytest -s shows them).
+
+Tolerances are the ones of the existing test of the same kernel (tests/test_gpu_unet.py), or are derived where they are used:
+  convolution, fp32 out       rtol 2e-4, atol 2e-4 * sqrt(9 * c_in)         (test_conv3x3_forward_dgrad_wgrad)
+  GroupNorm y (bf16)          rtol 1e-2, atol 1e-2                          (test_groupnorm_swish_dropout_fwd_bwd)
+  S = q k^T, fp32             rtol 1e-4, atol 1e-3 * sqrt(C / 64)           (test_batched_gemm_and_softmax, C = 64 there)
+  P = softmax (bf16)          rtol 1e-2, atol 2e-3                          (same)
+  bf16 products               rtol 1e-2, atol 1e-2                          (same)
+  bgemm, fp32 out             rtol 2e-4, atol 2e-4 * sqrt(K)                (the convolution's bound with K for 9 * c_in)
+"""
+import ctypes
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ERR_ARG = 1001                 # SFRON_ERR_ARG (csrc/common.h)
+GIB = 1 << 30
+
+
+def _gen(seed):
+    return torch.Generator(device=DEV).manual_seed(seed)
+
+
+def _free():
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+
+def _check(got, ref, rtol, atol, what):
+    """|got - ref| <= atol + rtol |ref| for every element (fp64 on the device); prints the largest error, names the worst element."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
+    over = (got - ref).abs() - (atol + rtol * ref.abs())
+    worst = int(over.argmax())
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), got.shape))
+    err = float((got - ref).abs().max())
+    print(f"[large] {what}: max |err| {err:.3e} (atol {atol:.3e}, rtol {rtol:.1e}), {int((over > 0).sum())} of {got.numel()} over")
+    assert float(over.max()) <= 0.0, (f"{what}: {int((over > 0).sum())} of {got.numel()} elements out of tolerance; worst at {idx}: got "
+                                      f"{float(got.flatten()[worst])!r}, want {float(ref.flatten()[worst])!r}")
+
+
+# ------------------------------------------------------------------------------------------------ 1. convolution
+def _conv_ref(x, w, bias, form):
+    """fp64 3x3 convolution of NHWC x [B, H, W, ci] with w [co, ci, 3, 3] as nine shifted products: "same" (pad 1), "down" (the (0,1,0,1)-pad
+    stride-2 Downsample), "up" (nearest x2, then pad 1).  Returns [B, ho, wo, co]."""
+    x, w = x.double(), w.double()
+    if form == "up":
+        x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    B, H, W, _ = x.shape
+    if form == "down":
+        xp, s, ho, wo = F.pad(x, (0, 0, 0, 1, 0, 1)), 2, H // 2, W // 2
+    else:
+        xp, s, ho, wo = F.pad(x, (0, 0, 1, 1, 1, 1)), 1, H, W
+    out = bias.double().view(1, 1, 1, -1).expand(B, ho, wo, w.shape[0]).clone()
+    for kh in range(3):
+        for kw in range(3):
+            out += xp[:, kh:kh + s * ho:s, kw:kw + s * wo:s, :] @ w[:, :, kh, kw].t()
+    return out
+
+
+class _Conv:
+    """One 3x3 convolution as vae._conv3 launches it: sfron_conv_wprep once, then sfron_conv_fwd with fp32 output, bias and optional resid."""
+
+    def __init__(self, ci, co, seed, ints=False):
+        from sfron import _lib, unet
+        from sfron._lib import check, ptr, stream_ptr
+        self.ci, self.co, self.cip, self.cop = ci, co, unet._pad8(ci), unet._pad8(co)
+        g = _gen(seed)
+        if ints:
+            w = torch.randint(-3, 4, (co, ci, 3, 3), generator=g, device=DEV).float()
+            bias = torch.randint(-3, 4, (co,), generator=g, device=DEV).float()
+        else:
+            w = torch.randn(co, ci, 3, 3, generator=g, device=DEV) * 0.1
+            bias = torch.randn(co, generator=g, device=DEV) * 0.1
+        self.wq, self.bias = w.to(torch.bfloat16).float(), bias          # the kernel's weights are the bf16 rounding of w
+        self.wf = torch.empty(self.cop * 9 * self.cip, dtype=torch.bfloat16, device=DEV)
+        check(_lib.lib().sfron_conv_wprep(ptr(w), co, ci, 9, self.cop, self.cip, ptr(self.wf), None, stream_ptr()), "conv_wprep")
+        self.bias_p = torch.zeros(self.cop, device=DEV)
+        self.bias_p[:co] = bias
+
+    def rows(self, x):
+        """NHWC fp32 (bf16-representable) [B, H, W, ci] -> the kernel's bf16 rows [B*H*W][cip], padded channels zero."""
+        B, H, W, ci = x.shape
+        if self.cip == ci:
+            return x.reshape(B * H * W, ci).to(torch.bfloat16)
+        r = torch.zeros(B * H * W, self.cip, dtype=torch.bfloat16, device=DEV)
+        r[:, :ci] = x.reshape(B * H * W, ci).to(torch.bfloat16)
+        return r
+
+    def run(self, xr, B, H, W, form, resid=None, out=None):
+        from sfron import _lib, unet
+        from sfron._lib import check, ptr, stream_ptr
+        ho, wo, stride, pad, up = {"same": (H, W, 1, 1, 0), "down": (H // 2, W // 2, 2, 0, 0), "up": (2 * H, 2 * W, 1, 1, 1)}[form]
+        if out is None:
+            out = torch.full((B * ho * wo, self.cop), float("nan"), dtype=torch.float32, device=DEV)
+        d = unet._conv_desc(B, H, W, self.cip, ho, wo, self.cop, 9, stride, pad, up, 0, bias=self.bias_p, resid=resid, out_f32=out, ld_out=self.cop)
+        check(_lib.lib().sfron_conv_fwd(ctypes.byref(d), ptr(xr), ptr(self.wf), stream_ptr()), "conv_fwd")
+        return out.view(B, ho, wo, self.cop)
+
+
+def _conv_regions(got, ref, rtol, atol, what):
+    """got / ref [B, ho, wo, co]: the four borders and the last 256 output rows of the last sample on their own, then every element."""
+    co = ref.shape[-1]
+    _check(got[:, 0], ref[:, 0], rtol, atol, what + " top border")
+    _check(got[:, -1], ref[:, -1], rtol, atol, what + " bottom border")
+    _check(got[:, :, 0], ref[:, :, 0], rtol, atol, what + " left border")
+    _check(got[:, :, -1], ref[:, :, -1], rtol, atol, what + " right border")
+    _check(got[-1].reshape(-1, co)[-256:], ref[-1].reshape(-1, co)[-256:], rtol, atol, what + " last 256 rows of the last sample")
+    _check(got, ref, rtol, atol, what + " every element")
+
+
+CONV_CASES = [  # (B, H, W, c_in, c_out, form, resid)
+    (2, 256, 256, 128, 128, "same", True), (2, 256, 256, 3, 128, "same", False), (2, 256, 256, 128, 3, "same", False),
+    (2, 256, 256, 128, 128, "down", False), (2, 128, 128, 256, 256, "up", False), (2, 64, 64, 512, 512, "same", True),
+    (1, 512, 512, 128, 128, "same", False),
+    (2, 192, 320, 128, 128, "same", False), (2, 320, 192, 256, 256, "down", False), (2, 192, 320, 128, 128, "up", True),   # H != W, pipelined tile
+    (3, 24, 40, 64, 64, "same", True), (3, 40, 24, 64, 64, "down", False),                                                # H != W, pixels % 256 != 0
+]
+
+
+@pytest.mark.parametrize("B,H,W,ci,co,form,resid", CONV_CASES)
+def test_conv3x3_at_vae_shapes(B, H, W, ci, co, form, resid):
+    g = _gen(B * H + W + ci + co)
+    cv = _Conv(ci, co, seed=ci * 7 + co)
+    x = torch.randn(B, H, W, ci, generator=g, device=DEV).to(torch.bfloat16).float()
+    ref = _conv_ref(x, cv.wq, cv.bias, form)
+    r = None
+    if resid:
+        r = torch.zeros(ref.shape[0] * ref.shape[1] * ref.shape[2], cv.cop, device=DEV)
+        r[:, :co] = torch.randn(r.shape[0], co, generator=g, device=DEV)
+        ref = ref + r.view(*ref.shape[:3], cv.cop)[..., :co].double()
+    got = cv.run(cv.rows(x), B, H, W, form, resid=r)
+    _conv_regions(got[..., :co], ref, 2e-4, 2e-4 * math.sqrt(9 * ci), f"conv {B}x{H}x{W} {ci}->{co} {form}")
+    if cv.cop != co:
+        assert float(got[..., co:].abs().max()) == 0.0, "padded output columns must stay exactly 0"
+    _free()
+
+
+@pytest.mark.parametrize("B,H,W,ci,co,form", [(2, 256, 256, 3, 3, "same"), (2, 192, 320, 3, 3, "same"), (2, 320, 192, 64, 64, "same"),
+                                               (2, 192, 320, 64, 64, "down"), (2, 96, 160, 64, 64, "up"), (3, 24, 40, 64, 64, "same"),
+                                               (3, 40, 24, 8, 8, "down")])
+def test_conv3x3_small_integers_are_bit_exact(B, H, W, ci, co, form):
+    """Inputs, weights and bias integers in [-3, 3]: every product and every partial sum is an integer of magnitude at most
+    9 * 64 * 9 + 3 < 2^24, exact in bf16 operands and fp32 accumulation in any order -- the result must equal the fp64 reference bit for bit.
+    A swapped H / W stride or a wrong tap at an edge fails without any tolerance.  3 -> 3 runs padded to 8 -> 8, as conv_in / conv_out do."""
+    g = _gen(H * 3 + W + ci)
+    cv = _Conv(ci, co, seed=H + ci, ints=True)
+    x = torch.randint(-3, 4, (B, H, W, ci), generator=g, device=DEV).float()
+    ref = _conv_ref(x, cv.wq, cv.bias, form)
+    got = cv.run(cv.rows(x), B, H, W, form)
+    assert float(ref.abs().max()) < 2 ** 24
+    _conv_regions(got[..., :co], ref, 0.0, 0.0, f"exact conv {B}x{H}x{W} {ci}->{co} {form}")
+    if cv.cop != co:
+        assert float(got[..., co:].abs().max()) == 0.0
+    _free()
+
+
+# ------------------------------------------------------------------------------------------------ 2. GroupNorm
+def _gn_run(x, gamma, beta, B, HW, C, swish, scratch):
+    from sfron import _lib
+    from sfron._lib import check, ptr, stream_ptr
+    L = _lib.lib()
+    y = torch.full((B * HW, C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    mean = torch.full((B * 32,), float("nan"), dtype=torch.float32, device=DEV)
+    rstd = torch.full_like(mean, float("nan"))
+    ws = torch.empty(L.sfron_groupnorm_scratch_bytes(B, HW, C, 32) // 4 + 4, dtype=torch.float32, device=DEV) if scratch else None    # vae._gn's size
+    check(L.sfron_groupnorm_fwd(ptr(x), C, ptr(gamma), ptr(beta), B, HW, C, 32, 1e-6, int(swish), None, 1.0, ptr(y), ptr(mean), ptr(rstd),
+                                ptr(ws), stream_ptr()), "groupnorm_fwd")
+    return y, mean, rstd
+
+
+def _gn_ref(x, gamma, beta, B, HW, C, swish):
+    """F.group_norm in fp64 and the fp64 group statistics of the fp32 input x [B*HW][C]."""
+    xd = x.double().view(B, HW, C)
+    z = F.group_norm(xd.permute(0, 2, 1), 32, gamma.double(), beta.double(), eps=1e-6)
+    if swish:
+        z = z * torch.sigmoid(z)
+    grp = xd.view(B, HW, 32, C // 32)
+    mean = grp.mean(dim=(1, 3))
+    var = grp.var(dim=(1, 3), unbiased=False)
+    return z.permute(0, 2, 1).reshape(B * HW, C), mean.reshape(-1), (var + 1e-6).rsqrt().reshape(-1)
+
+
+def _gn_check(x, gamma, beta, B, HW, C, what):
+    from sfron import _lib
+    one = _lib.lib().sfron_groupnorm_one_launch(B, HW, C, 32)
+    for swish in (1, 0):
+        zr, mr, rr = _gn_ref(x, gamma, beta, B, HW, C, swish)
+        for scratch in (True, False):          # the row-coalesced family the rule picks (one launch / two phases), then the per-(sample, group) kernel
+            name = f"{what} swish {swish} " + (("one-launch" if one else "two-phase") if scratch else "per-group")
+            y, mean, rstd = _gn_run(x, gamma, beta, B, HW, C, swish, scratch)
+            # mean and rstd are fp64 results rounded once to fp32 (2^-24 relative); 1e-6 leaves room for the final division and rsqrt
+            _check(mean, mr, 1e-6, 1e-6, name + " mean")
+            _check(rstd, rr, 1e-4, 0.0, name + " rstd")
+            _check(y, zr, 1e-2, 1e-2, name + " y")
+            del y
+        del zr
+    _free()
+
+
+GN_SHAPES = [(2, 65536, 128), (1, 262144, 128), (2, 16384, 256), (16, 4096, 512), (2, 192 * 320, 128), (3, 24 * 40, 128), (3, 25 * 40, 128)]
+
+
+@pytest.mark.parametrize("B,HW,C", GN_SHAPES)
+def test_groupnorm_at_vae_shapes(B, HW, C):
+    """(3, 960, 128): 32 chunks of 30 rows, not a multiple of the rows a workgroup takes per pass; (3, 1000, 128): 1000 pixels do not divide
+    into the 32 chunks of the two-phase form at all."""
+    g = _gen(B + HW + C)
+    x = torch.randn(B * HW, C, generator=g, device=DEV) * 1.5 + 0.3
+    gamma, beta = torch.randn(C, generator=g, device=DEV) * 0.5 + 1.0, torch.randn(C, generator=g, device=DEV) * 0.2
+    _gn_check(x, gamma, beta, B, HW, C, f"GroupNorm {B}x{HW}x{C}")
+
+
+@pytest.mark.parametrize("B,HW,C", GN_SHAPES)
+def test_groupnorm_large_mean_needs_fp64_statistics(B, HW, C):
+    """x = offset_g + 0.05 * randn with offset_g = 12 + 0.25 * (g % 8) per channel group g: the variance (2.5e-3) is 1e-5 of E[x^2], so
+    E[x^2] - E[x]^2 survives only in fp64.  The kernels accumulate in double; this pins that against a later "faster statistics" change.
+    Condition: rstd within 1e-4 relative of the fp64 value.  Restated on the CPU for one group of each shape used here at offset 12 (numpy,
+    fp32 single pass with pairwise partial sums | fp64 single pass), relative error of rstd:
+      4 ch x 65536: 6.9e-3 | 4.1e-12     4 ch x 262144: 5.6e-3 | 6.6e-12     8 ch x 16384: 4.2e-3 | 1.9e-12
+      16 ch x 4096: 1.3e-3 | 5.7e-12     4 ch x 61440:  2.4e-3 | 5.7e-12     4 ch x 960:   1.5e-3 | 8.5e-12
+      4 ch x 1000:  1.2e-3 | 1.9e-12
+    so 1e-4 separates the two by more than an order of magnitude each way at every shape.  (At the issue's offset 8 the fp32 restatement
+    of 8 ch x 16384 happened to land at 1.3e-5: not discriminating, hence 12.)"""
+    g = _gen(B * 3 + HW + C)
+    off = (12.0 + 0.25 * (torch.arange(32, device=DEV) % 8)).repeat_interleave(C // 32)
+    x = (off.double() + 0.05 * torch.randn(B * HW, C, generator=g, device=DEV, dtype=torch.float64)).float()
+    gamma, beta = torch.randn(C, generator=g, device=DEV) * 0.5 + 1.0, torch.randn(C, generator=g, device=DEV) * 0.2
+    _gn_check(x, gamma, beta, B, HW, C, f"GroupNorm offset {B}x{HW}x{C}")
+
+
+# ------------------------------------------------------------------------------------------------ 3. attention pieces, 1x1 shortcut
+@pytest.mark.parametrize("B,T", [(2, 1024), (2, 4096), (1, 32 * 48)])
+def test_attention_stages_as_the_vae_runs_them(B, T):
+    """The call sequence of vae._attn, C = 512, each stage against torch on that stage's OWN inputs (the kernel's previous output), so errors
+    do not compound.  Unit-variance q and k give scores of standard deviation sqrt(C) before and about 1 after the C^-0.5 scale."""
+    from sfron import _lib
+    from sfron._lib import check, ptr, stream_ptr
+    from sfron.unet import bgemm
+    L, C, rows = _lib.lib(), 512, B * T
+    g = _gen(T + B)
+    hn = torch.randn(rows, C, generator=g, device=DEV).to(torch.bfloat16)
+    wqkv = (torch.randn(3 * C, C, generator=g, device=DEV) * C ** -0.5).to(torch.bfloat16)
+    bqkv = torch.randn(3 * C, generator=g, device=DEV) * 0.1
+    qkv = torch.full((rows, 3 * C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    bgemm(hn, wqkv, rows, 3 * C, C, lda=C, ldb=C, bias=bqkv, c_bf16=qkv, ldc=3 * C)
+    _check(qkv, hn.double() @ wqkv.double().t() + bqkv.double(), 1e-2, 1e-2, f"qkv T={T}")
+    q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C
+    qd, kd, vd = (t.double() for t in qkv.view(B, T, 3, C).unbind(2))
+    S = torch.full((B * T, T), float("nan"), dtype=torch.float32, device=DEV)
+    bgemm(q, k, T, T, C, lda=3 * C, ldb=3 * C, batch=B, sa=T * 3 * C, sb=T * 3 * C, sc=T * T, c_f32=S, ldc=T)
+    _check(S.view(B, T, T), qd @ kd.transpose(1, 2), 1e-4, 1e-3 * math.sqrt(C / 64), f"S T={T}")
+    P = torch.full((B * T, T), float("nan"), dtype=torch.bfloat16, device=DEV)
+    scale = float(int(C) ** (-0.5))
+    check(L.sfron_softmax_fwd(ptr(S), B * T, T, T, scale, ptr(P), stream_ptr()), "softmax_fwd")
+    _check(P, torch.softmax(S.double() * scale, dim=-1), 1e-2, 2e-3, f"P T={T}")
+    _row_sums(P, f"P T={T}")
+    O = torch.full((rows, C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    bgemm(P, v, T, C, T, lda=T, ldb=3 * C, b_t=True, batch=B, sa=T * T, sb=T * 3 * C, sc=T * C, c_bf16=O, ldc=C)
+    _check(O.view(B, T, C), P.double().view(B, T, T) @ vd, 1e-2, 1e-2, f"O T={T}")
+    wp = (torch.randn(C, C, generator=g, device=DEV) * C ** -0.5).to(torch.bfloat16)
+    bp = torch.randn(C, generator=g, device=DEV) * 0.1
+    x = torch.randn(rows, C, generator=g, device=DEV)
+    out = torch.full((rows, C), float("nan"), dtype=torch.float32, device=DEV)
+    bgemm(O, wp, rows, C, C, lda=C, ldb=C, bias=bp, c_f32=out, ldc=C, resid=x)
+    _check(out, O.double() @ wp.double().t() + bp.double() + x.double(), 2e-4, 2e-4 * math.sqrt(C), f"proj_out T={T}")
+    _free()
+
+
+def _row_sums(P, what):
+    """Every row of the bf16 probabilities sums to 1 within 2^-9 + 1e-3: 2^-9 for the rounding of the terms to bf16 (see
+    test_softmax_rows_of_4096 for how much of it the rounding alone can use), 1e-3 for __expf and the fp32 sum of the row."""
+    s = P.double().sum(-1)
+    dev = float((s - 1.0).abs().max())
+    print(f"[large] {what}: max |row sum - 1| {dev:.3e} (bound {2 ** -9 + 1e-3:.3e})")
+    assert dev <= 2 ** -9 + 1e-3, (what, dev)
+
+
+@pytest.mark.parametrize("std", [1.0, 6.0])
+def test_softmax_rows_of_4096(std):
+    """n = 4096 with scores of standard deviation 1 and 6 (drawn on the CPU, so the figures below can be reproduced without a GPU).  The
+    reference's own deviation of a row sum from 1 (torch fp64 softmax rounded to bf16) over these 1024 rows is 1.6e-4 / 1.7e-4 (std 1,
+    n_valid 4096 / 4000) and 2.54e-3 / 2.60e-3 (std 6), inside the 2.95e-3 bound of _row_sums; the test prints it again.  Also: a padded
+    case (n 4096, n_valid 4000: columns 4000 .. 4095 exactly 0), and rows holding one score 60 above the rest (P = 1 there, everything
+    finite).
+    About the bound: bf16 keeps 8 significant bits, so round-to-nearest is off by up to 2^-8 relative (half an ulp just above a power of two),
+    not 2^-9; a row dominated by one or two terms can therefore sit above 2^-9 = 1.95e-3 through rounding alone, as the std 6 reference
+    does.  The bound is kept as the project set it; with these inputs the reference leaves 3.5e-4 of it, thirty times the 1e-5 by
+    which the kernel's row sums differ from the reference's."""
+    from sfron import _lib
+    from sfron._lib import check, ptr, stream_ptr
+    L, rows, n = _lib.lib(), 1024, 4096
+    g = torch.Generator().manual_seed(int(std) + 11)
+    S = (torch.randn(rows, n, generator=g) * std).to(DEV)
+    hot = torch.randint(0, 4000, (rows,), generator=g).to(DEV)
+    S[::64] = S[::64].clamp(max=3.0 * std)
+    S[torch.arange(0, rows, 64, device=DEV), hot[::64]] = 3.0 * std + 60.0          # every 64th row: one score 60 above all others
+    for nv in (n, 4000):
+        P = torch.full((rows, n), float("nan"), dtype=torch.bfloat16, device=DEV)
+        check(L.sfron_softmax_fwd(ptr(S), rows, n, nv, 1.0, ptr(P), stream_ptr()), "softmax_fwd")
+        ref = torch.zeros(rows, n, dtype=torch.float64, device=DEV)
+        ref[:, :nv] = torch.softmax(S[:, :nv].double(), dim=-1)
+        print(f"[large] softmax std {std} n_valid {nv}: the reference rounded to bf16 deviates from row sum 1 by "
+              f"{float((ref.to(torch.bfloat16).double().sum(-1) - 1).abs().max()):.3e}")
+        assert bool(torch.isfinite(P.float()).all())
+        _check(P, ref, 1e-2, 2e-3, f"softmax std {std} n_valid {nv}")
+        _row_sums(P, f"softmax std {std} n_valid {nv}")
+        if nv < n:
+            assert float(P[:, nv:].float().abs().max()) == 0.0, "padding columns must be exactly 0"
+        assert bool((P[torch.arange(0, rows, 64, device=DEV), hot[::64]].float() == 1.0).all()), "a score 60 above the rest takes P = 1"
+    _free()
+
+
+@pytest.mark.parametrize("M,N,K", [(2 * 65536, 256, 128), (2 * 16384, 512, 256)])
+def test_shortcut_1x1_product_at_vae_shapes(M, N, K):
+    """nin_shortcut of a ResnetBlock: bgemm with bias, fp32 out, M = every pixel of the batch."""
+    from sfron.unet import bgemm
+    g = _gen(M + N)
+    a = torch.randn(M, K, generator=g, device=DEV).to(torch.bfloat16)
+    w = (torch.randn(N, K, generator=g, device=DEV) * 0.1).to(torch.bfloat16)
+    bias = torch.randn(N, generator=g, device=DEV) * 0.1
+    out = torch.full((M, N), float("nan"), dtype=torch.float32, device=DEV)
+    bgemm(a, w, M, N, K, lda=K, ldb=K, bias=bias, c_f32=out, ldc=N)
+    ref = a.double() @ w.double().t() + bias.double()
+    _check(out[-256:], ref[-256:], 2e-4, 2e-4 * math.sqrt(K), f"shortcut {M}x{N}x{K} last 256 rows")
+    _check(out, ref, 2e-4, 2e-4 * math.sqrt(K), f"shortcut {M}x{N}x{K}")
+    _free()
+
+
+# ------------------------------------------------------------------------------------------------ 4a. just under 2 GiB
+@pytest.mark.parametrize("B,H,ci,co,form", [(56, 256, 128, 128, "same"), (16, 128, 256, 256, "up")])
+def test_conv_operand_just_under_2gib(B, H, ci, co, form):
+    """(56, 256 x 256, 128 -> 128): the fp32 output is 1.75 GiB, the source 0.875 GiB.  (16, 128 -> 256 px, 256 channels, nearest x2): the default
+    decoder chunk, an output of exactly 1 GiB.  The first and the last sample against the fp64 reference, every sample against the same
+    sample run alone as a batch of one (one launch of the full batch, B launches of one)."""
+    g = _gen(B + ci)
+    cv = _Conv(ci, co, seed=B)
+    x = torch.randn(B, H, H, ci, generator=g, device=DEV).to(torch.bfloat16)
+    xr = x.view(B * H * H, ci)
+    got = cv.run(xr, B, H, H, form)
+    nbytes = got.numel() * 4
+    assert (GIB <= nbytes < 2 * GIB) and (form != "same" or nbytes >= 1.5 * GIB), nbytes
+    atol = 2e-4 * math.sqrt(9 * ci)
+    for b in (0, B - 1):
+        _conv_regions(got[b:b + 1], _conv_ref(x[b:b + 1].float(), cv.wq, cv.bias, form), 2e-4, atol, f"conv B={B} {form} sample {b}")
+    same = 0
+    for b in range(B):
+        alone = cv.run(xr[b * H * H:(b + 1) * H * H], 1, H, H, form)
+        same += int(torch.equal(alone[0], got[b]))
+        if not torch.equal(alone[0], got[b]):
+            _check(got[b], alone[0], 2e-4, atol, f"conv B={B} {form} sample {b} in the batch against alone")
+    print(f"[large] conv B={B} {form}: {same} of {B} samples bit-identical to the sample run alone")
+    del got, x, xr
+    _free()
+
+
+def test_groupnorm_operand_just_under_2gib():
+    """(56, 65 536, 128): the fp32 input is 1.75 GiB.  First and last sample against fp64, every sample against the sample run alone (the
+    chunk count differs with the batch size, so the partial sums may be added in another order: the reference tolerance, not equality)."""
+    B, HW, C = 56, 65536, 128
+    g = _gen(56)
+    x = torch.randn(B * HW, C, generator=g, device=DEV) * 1.5 + 0.3
+    assert 1.5 * GIB <= x.numel() * 4 < 2 * GIB
+    gamma, beta = torch.randn(C, generator=g, device=DEV) * 0.5 + 1.0, torch.randn(C, generator=g, device=DEV) * 0.2
+    y, mean, rstd = _gn_run(x, gamma, beta, B, HW, C, 1, True)
+    for b in (0, B - 1):
+        zr, mr, rr = _gn_ref(x[b * HW:(b + 1) * HW], gamma, beta, 1, HW, C, 1)
+        _check(mean[32 * b:32 * b + 32], mr, 1e-6, 1e-6, f"GroupNorm B=56 sample {b} mean")
+        _check(rstd[32 * b:32 * b + 32], rr, 1e-4, 0.0, f"GroupNorm B=56 sample {b} rstd")
+        _check(y[b * HW:(b + 1) * HW], zr, 1e-2, 1e-2, f"GroupNorm B=56 sample {b} y")
+    same = 0
+    for b in range(B):
+        y1, m1, r1 = _gn_run(x[b * HW:(b + 1) * HW], gamma, beta, 1, HW, C, 1, True)
+        eq = torch.equal(y1, y[b * HW:(b + 1) * HW])
+        same += int(eq)
+        if not eq:
+            _check(y[b * HW:(b + 1) * HW], y1, 1e-2, 1e-2, f"GroupNorm B=56 sample {b} in the batch against alone")
+        _check(rstd[32 * b:32 * b + 32], r1, 1e-4, 0.0, f"GroupNorm B=56 sample {b} rstd against alone")
+    print(f"[large] GroupNorm B=56: {same} of {B} samples bit-identical to the sample run alone")
+    del x, y
+    _free()
+
+
+def test_softmax_and_cast_are_64_bit_clean_above_2gib():
+    """sfron_softmax_fwd and sfron_cast_rows_bf16 index with int64_t and are NOT refused above the line: a 2.125 GiB score matrix
+    (139 264 rows of 4096) and a 2 GiB + 512 KiB activation (2^22 + 1024 rows of 128), every element compared (the cast exactly)."""
+    from sfron import _lib
+    from sfron._lib import check, ptr, stream_ptr
+    L = _lib.lib()
+    rows, n = 34 * 4096, 4096
+    g = _gen(77)
+    S = torch.randn(rows, n, generator=g, device=DEV)
+    assert S.numel() * 4 > 2 * GIB
+    P = torch.full((rows, n), float("nan"), dtype=torch.bfloat16, device=DEV)
+    check(L.sfron_softmax_fwd(ptr(S), rows, n, n, 1.0, ptr(P), stream_ptr()), "softmax_fwd")
+    for r0 in range(0, rows, 16384):
+        _check(P[r0:r0 + 16384], torch.softmax(S[r0:r0 + 16384].double(), dim=-1), 1e-2, 2e-3, f"softmax above 2 GiB rows {r0}..")
+    _row_sums(P[-16384:], "softmax above 2 GiB, last rows")
+    del S, P
+    _free()
+    rows, C = (1 << 22) + 1024, 128
+    x = torch.randn(rows, C, generator=g, device=DEV)
+    assert x.numel() * 4 > 2 * GIB
+    y = torch.full((rows, C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    check(L.sfron_cast_rows_bf16(ptr(x), C, rows, C, ptr(y), stream_ptr()), "cast_rows_bf16")
+    assert torch.equal(y, x.to(torch.bfloat16)), "cast above 2 GiB: not the round-to-nearest-even bf16 of every element"
+    del x, y
+    _free()
+
+
+# ------------------------------------------------------------------------------------------------ 4b. at and over 2 GiB: refused
+def _untouched(t, what):
+    """The sentinel the test wrote into the first and last KiB of an output is still there: nothing was launched."""
+    f = t.view(-1)
+    assert bool((f[:512] == 7).all()) and bool((f[-512:] == 7).all()), f"{what}: the refused call wrote its output"
+
+
+def _sentinel(t):
+    f = t.view(-1)
+    f[:512] = 7
+    f[-512:] = 7
+    return t
+
+
+def test_operands_of_2gib_are_refused_before_any_launch():
+    """Every descriptor below describes an operand of exactly 2^31 bytes and every pointer is a REAL allocation of the full size it describes, so
+    a missing check computes on memory the test owns instead of leaving it.  Each entry point must return SFRON_ERR_ARG and write nothing."""
+    from sfron import _lib, unet
+    from sfron._lib import ptr, stream_ptr
+    L = _lib.lib()
+    # sfron_conv_fwd: 128 -> 128 at 256 x 256, batch 64: the fp32 output is 64 * 65536 * 128 * 4 = 2^31 bytes
+    B, H, C = 64, 256, 128
+    xr = torch.zeros(B * H * H, C, dtype=torch.bfloat16, device=DEV)
+    wf = torch.zeros(C * 9 * C, dtype=torch.bfloat16, device=DEV)
+    bias = torch.zeros(C, device=DEV)
+    out = _sentinel(torch.zeros(B * H * H, C, dtype=torch.float32, device=DEV))
+    assert out.numel() * 4 == 1 << 31
+    d = unet._conv_desc(B, H, H, C, H, H, C, 9, 1, 1, 0, 0, bias=bias, out_f32=out, ld_out=C)
+    assert L.sfron_conv_fwd(ctypes.byref(d), ptr(xr), ptr(wf), stream_ptr()) == ERR_ARG
+    _untouched(out, "conv_fwd")
+    # sfron_groupnorm_fwd on the same 2^31-byte activation, both families
+    y = _sentinel(torch.zeros(B * H * H, C, dtype=torch.bfloat16, device=DEV))
+    mean, rstd, gamma = torch.zeros(B * 32, device=DEV), torch.zeros(B * 32, device=DEV), torch.ones(C, device=DEV)
+    ws = torch.empty(L.sfron_groupnorm_scratch_bytes(B, H * H, C, 32) // 4 + 4, dtype=torch.float32, device=DEV)
+    for scratch in (ws, None):
+        assert L.sfron_groupnorm_fwd(ptr(out), C, ptr(gamma), ptr(bias), B, H * H, C, 32, 1e-6, 1, None, 1.0, ptr(y), ptr(mean), ptr(rstd),
+                                     ptr(scratch), stream_ptr()) == ERR_ARG
+    _untouched(y, "groupnorm_fwd")
+    del out, y, xr
+    _free()
+    # sfron_conv_wgrad: batch 128: the source and dy are 128 * 65536 * 128 * 2 = 2^31 bytes each
+    B = 128
+    src = torch.zeros(B * H * H, C, dtype=torch.bfloat16, device=DEV)
+    dy = torch.zeros(B * H * H, C, dtype=torch.bfloat16, device=DEV)
+    assert src.numel() * 2 == 1 << 31
+    d = unet._conv_desc(B, H, H, C, H, H, C, 9, 1, 1, 0, 0)
+    nsl = max(1, L.sfron_conv_wgrad_splits(ctypes.byref(d)))
+    dw = _sentinel(torch.zeros(nsl * C * 9 * C, dtype=torch.float32, device=DEV))
+    assert L.sfron_conv_wgrad(ctypes.byref(d), ptr(dy), C, ptr(src), ptr(dw), stream_ptr()) == ERR_ARG
+    _untouched(dw, "conv_wgrad")
+    del dy, dw
+    # sfron_bgemm_bf16 and sfron_gemm_bf16: A = [2^23][128] bf16 = 2^31 bytes (the same allocation), N = 64
+    M, K, N = 1 << 23, 128, 64
+    a, w = src, torch.zeros(N, K, dtype=torch.bfloat16, device=DEV)
+    c = _sentinel(torch.zeros(M, N, dtype=torch.bfloat16, device=DEV))
+    bd = _lib.BGemmDesc()
+    bd.A, bd.B, bd.M, bd.N, bd.K, bd.lda, bd.ldb, bd.batch, bd.alpha = ptr(a), ptr(w), M, N, K, K, K, 1, 1.0
+    bd.c_bf16, bd.ldc = ptr(c), N
+    assert L.sfron_bgemm_bf16(ctypes.byref(bd), stream_ptr()) == ERR_ARG
+    _untouched(c, "bgemm_bf16")
+    gd = _lib.GemmDesc()
+    gd.A, gd.B, gd.M, gd.N, gd.K, gd.lda, gd.ldb, gd.epilogue, gd.alpha = ptr(a), ptr(w), M, N, K, K, K, _lib.EPI_BF16, 1.0
+    gd.c_bf16, gd.ldc_bf16 = ptr(c), N
+    assert L.sfron_gemm_bf16(ctypes.byref(gd), stream_ptr()) == ERR_ARG
+    _untouched(c, "gemm_bf16")
+    del a, src, c
+    _free()

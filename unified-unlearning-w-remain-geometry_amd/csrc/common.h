@@ -8,6 +8,14 @@
 #define SFRON_ERR_UNSUPPORTED 1002
 
 #define SFRON_CHECK_ARG(cond) do { if (!(cond)) return SFRON_ERR_ARG; } while (0)
+// Operand limit of the C entry points.  The pipelined tiles address their operands through buffer resources (a 32-bit byte count, 32-bit
+// byte offsets) and several launchers form a row count in `int`: an entry point that does either refuses -- SFRON_ERR_ARG before any
+// launch -- an operand whose extent, computed in 64-bit from its descriptor, reaches 2^31 bytes (the rule fp8.hip applies to its
+// products).  Entry points whose kernels index with int64_t / size_t throughout say so at their definition and take larger operands.
+// extent: bytes from the first element to one past the last of a [rows][ld] matrix whose rows hold `cols` elements of `elem` bytes.
+static inline int64_t sfron_extent(int64_t rows, int64_t ld, int64_t cols, int elem) { return rows > 0 ? ((rows - 1) * ld + cols) * elem : 0; }
+static inline bool sfron_fits31(int64_t bytes) { return bytes >= 0 && bytes < (1ll << 31); }
+
 #define SFRON_LAUNCH_STATUS() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

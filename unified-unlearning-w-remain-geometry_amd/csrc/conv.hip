@@ -2283,6 +2283,10 @@ int sfron_bgemm_bf16(const sfron_bgemm_desc* d, void* stream) {
   if (!d->a_transposed || !d->b_transposed) SFRON_CHECK_ARG(d->K % 8 == 0);
   if (d->a_transposed) SFRON_CHECK_ARG(d->M % 8 == 0);
   if (d->b_transposed) SFRON_CHECK_ARG(d->N % 8 == 0);
+  // 2 GiB rule, per matrix of the batch (the batch strides are 64-bit pointer steps): the pipelined tiles hold 32-bit byte offsets
+  SFRON_CHECK_ARG(sfron_fits31(d->a_transposed ? sfron_extent(d->K, d->lda, d->M, 2) : sfron_extent(d->M, d->lda, d->K, 2)) &&
+                  sfron_fits31(d->b_transposed ? sfron_extent(d->K, d->ldb, d->N, 2) : sfron_extent(d->N, d->ldb, d->K, 2)) &&
+                  sfron_fits31(sfron_extent(d->M, d->ldc, d->N, d->c_f32 ? 4 : 2)));
   BGemmArgs g{};
   g.A = (const __bf16*)d->A; g.B = (const __bf16*)d->B;
   g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb;
@@ -2367,6 +2371,9 @@ static int conv_geom(const sfron_conv_desc* d, ConvGeom& c, int src_c) {
   SFRON_CHECK_ARG(d->batch > 0 && d->h_src > 0 && d->w_src > 0 && d->h_out > 0 && d->w_out > 0 && (d->taps == 9 || d->taps == 1));
   SFRON_CHECK_ARG(d->stride == 1 || d->stride == 2);
   SFRON_CHECK_ARG(!(d->upsample && d->dilate) && src_c % 8 == 0);
+  // 2 GiB rule: the GEMM row count batch * h_out * w_out and the source pixel index are formed in `int` and the pipelined tiles read the
+  // source through a buffer resource (the generic tile they decline to is 64-bit in its offsets, but nothing runs it above the line)
+  SFRON_CHECK_ARG(sfron_fits31((int64_t)d->batch * d->h_src * d->w_src * src_c * 2) && (int64_t)d->batch * d->h_out * d->w_out < (1ll << 31));
   c.Hs = d->h_src; c.Ws = d->w_src; c.C = src_c; c.Ho = d->h_out; c.Wo = d->w_out;
   c.stride = d->stride; c.pad = d->pad; c.up = d->upsample; c.dil = d->dilate; c.taps = d->taps; c.flip = 0;
   return SFRON_OK;
@@ -2383,6 +2390,9 @@ int sfron_conv_fwd(const sfron_conv_desc* d, const uint16_t* src, const uint16_t
   g.lda = d->c_src; g.ldb = g.K;
   g.Cb = (__bf16*)d->out_bf16; g.Cf = d->out_f32; g.ldcb = g.ldcf = d->ld_out;
   SFRON_CHECK_ARG((g.Cb != nullptr) != (g.Cf != nullptr) && d->ld_out % 4 == 0 && d->ld_out >= d->n_out);
+  // the output (and `resid`, which shares its layout) and the weights, as the source in conv_geom
+  SFRON_CHECK_ARG(sfron_fits31(sfron_extent((int64_t)d->batch * d->h_out * d->w_out, d->ld_out, d->n_out, g.Cf ? 4 : 2)) &&
+                  sfron_fits31((int64_t)d->n_out * d->taps * d->c_src * 2));
   g.bias = d->bias; g.resid = d->resid; g.vec = d->sample_vec; g.ldvec = d->ld_vec; g.T = d->h_out * d->w_out;
   g.alpha = 1.0f; g.accumulate = d->accumulate;
   // few output pixels, deep contraction (the 16x16 / 8x8 levels of the LDM UNet: 512 x 1280 outputs over K = 11520..23040): split the
@@ -2469,6 +2479,8 @@ int sfron_conv_wgrad(const sfron_conv_desc* d, const uint16_t* dy, int ld_dy, co
   SFRON_CHECK_ARG(d && dy && src && dw_gemm && d->n_out % 8 == 0 && ld_dy % 8 == 0);
   BGemmArgs g{};
   int rc = conv_geom(d, g.cg, d->c_src); if (rc) return rc;
+  SFRON_CHECK_ARG(sfron_fits31(sfron_extent((int64_t)d->batch * d->h_out * d->w_out, ld_dy, d->n_out, 2)) &&
+                  sfron_fits31((int64_t)d->n_out * d->taps * d->c_src * 4));            // dy and one fp32 slab, as the source in conv_geom
   g.A = (const __bf16*)dy; g.B = (const __bf16*)src;
   g.M = d->n_out; g.N = d->taps * d->c_src; g.K = d->batch * d->h_out * d->w_out;
   g.lda = ld_dy; g.ldb = d->c_src;
@@ -2609,6 +2621,10 @@ int64_t sfron_groupnorm_scratch_bytes(int B, int HW, int C, int groups) {
   const int64_t f = (int64_t)B * n * groups * 2 * sizeof(double), bw = (int64_t)B * n * C * 2 * sizeof(float);
   return f > bw ? f : bw;
 }
+// 2 GiB rule for the GroupNorm family: the kernels step through x / y / dy / dx with size_t offsets, but the chunk and workgroup
+// bookkeeping (B * chunks, rows per chunk) is `int` and nothing runs them above the line -- a [B][HW][ld] fp32 activation of 2^31 bytes
+// or more is refused (its bf16 result is half that)
+static bool gn_fits31(int B, int HW, int ld) { return sfron_fits31((int64_t)B * HW * ld * 4); }
 static bool gn2_ok(int ldx, int ld2, int C, int groups, const void* scratch) {
   return scratch && C % 4 == 0 && ldx % 4 == 0 && ld2 % 4 == 0 && C <= GN_MAXQ * 4 * GNB && groups <= 64 && ((uintptr_t)scratch & 15) == 0;
 }
@@ -2641,6 +2657,7 @@ int sfron_groupnorm_fwd(const float* x, int ldx, const float* gamma, const float
                         int swish, const uint8_t* drop_mask, float drop_scale, uint16_t* y, float* mean, float* rstd, void* scratch,
                         void* stream) {
   SFRON_CHECK_ARG(x && gamma && beta && y && mean && rstd && groups > 0 && C % groups == 0 && ldx >= C && C / groups <= TPB);
+  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
   if (gn2_ok(ldx, C, C, groups, scratch) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0)) {
     if (const int gpb = gn3_gpb(B, HW, C, groups)) {
       hipLaunchKernelGGL(k_gn3_fwd<false>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, x, ldx, gamma, beta, HW, C, groups, gpb, eps, swish,
@@ -2673,6 +2690,7 @@ int sfron_groupnorm_bwd_res(const float* dy, const float* x, int ldx, const floa
                             float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma, float* part_beta,
                             void* scratch, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0);
+  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
   const int cg = C / groups;
   SFRON_CHECK_ARG(cg <= TPB);
   SFRON_CHECK_ARG(!extra || (ld_extra >= C && extra != dx));
@@ -2716,7 +2734,7 @@ int sfron_groupnorm_bwd_cast(const float* dy, const float* x, int ldx, const flo
                              const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
                              uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* scratch, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && scratch);
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0);
+  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
   SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)scratch) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 &&
                   (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
   const int nchunk = gn_chunks(B, HW);
@@ -2767,6 +2785,7 @@ int sfron_groupnorm_one_launch(int B, int HW, int C, int groups) {
 int sfron_groupnorm_fwd_src(const sfron_split_src* src, float* x, const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps,
                             int swish, const uint8_t* drop_mask, float drop_scale, uint16_t* y, float* mean, float* rstd, void* stream) {
   SFRON_CHECK_ARG(x && gamma && beta && y && mean && rstd && groups > 0 && C % groups == 0 && split_src_ok(src, C));
+  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, C));
   SFRON_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0) && groups <= 64);
   SFRON_CHECK_ARG(!src->resid || (const float*)x != src->resid);
   const int gpb = gn3_gpb(B, HW, C, groups);
@@ -2781,6 +2800,7 @@ int sfron_groupnorm_bwd_res_src(const sfron_split_src* src, float* dy, const flo
                                 float drop_scale, float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma,
                                 float* part_beta, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0 && split_src_ok(src, C));
+  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
   SFRON_CHECK_ARG(ldx % 4 == 0 && lddx % 4 == 0 && groups <= 64 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 &&
                   (!drop_mask || ((uintptr_t)drop_mask & 3) == 0) && dy != dx);
   SFRON_CHECK_ARG(!extra || (ld_extra >= C && extra != dx && ld_extra % 4 == 0 && ((uintptr_t)extra & 15) == 0));
@@ -2796,7 +2816,7 @@ int sfron_groupnorm_bwd_cast_src(const sfron_split_src* src, float* dy, const fl
                                  const float* mean, const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask,
                                  float drop_scale, uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && split_src_ok(src, C));
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0);
+  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
   SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
   const int gpb = gn3_gpb(B, HW, C, groups);
   if (!gpb) return SFRON_ERR_UNSUPPORTED;
@@ -2807,8 +2827,10 @@ int sfron_groupnorm_bwd_cast_src(const sfron_split_src* src, float* dy, const fl
   return SFRON_OK;
 }
 
+// No 2 GiB limit: k_softmax_fwd / k_softmax_bwd take the row index as int64_t and form row * n in 64-bit; one wave per row, four rows per
+// workgroup, so the only 32-bit quantity is the grid (rows / 4 < 2^31).  tests/test_gpu_large_shapes.py runs a score matrix above 2 GiB.
 int sfron_softmax_fwd(const float* s, int64_t rows, int n, int n_valid, float scale, uint16_t* p, void* stream) {
-  SFRON_CHECK_ARG(s && p && rows > 0 && n > 0 && n_valid > 0 && n_valid <= n);
+  SFRON_CHECK_ARG(s && p && rows > 0 && n > 0 && n_valid > 0 && n_valid <= n && (rows + 3) / 4 < (1ll << 31));
   hipLaunchKernelGGL(k_softmax_fwd, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, (hipStream_t)stream, s, rows, n, n_valid, scale, (__bf16*)p);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
@@ -2879,7 +2901,7 @@ int sfron_geglu_bwd(const float* d_out, const float* h, int64_t rows, int F, uin
 }
 
 int sfron_softmax_bwd(const uint16_t* p, const float* dp, int64_t rows, int n, float scale, uint16_t* ds, void* stream) {
-  SFRON_CHECK_ARG(p && dp && ds && rows > 0 && n > 0);
+  SFRON_CHECK_ARG(p && dp && ds && rows > 0 && n > 0 && (rows + 3) / 4 < (1ll << 31));
   hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, (hipStream_t)stream, (const __bf16*)p, dp, rows, n, scale, (__bf16*)ds);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
@@ -2913,6 +2935,8 @@ int sfron_pool2_sum(const float* dy, int B, int H, int W, int C, float* dx, int 
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }
+// No 2 GiB limit: k_cast_rows / k_cast_rows4 (and the k_copy_cols family below) carry the row as int64_t and form r * ldx in 64-bit; the
+// row-chunk grid stays below 65536.  tests/test_gpu_large_shapes.py casts an activation above 2 GiB.
 int sfron_cast_rows_bf16(const float* x, int ldx, int64_t rows, int C, uint16_t* y, void* stream) {
   SFRON_CHECK_ARG(x && y && ldx >= C);
   if (C % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 7) == 0) {

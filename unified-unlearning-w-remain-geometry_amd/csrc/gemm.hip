@@ -1924,6 +1924,10 @@ int sfron_gemm_bf16(const sfron_gemm_desc* d, void* stream) {
   SFRON_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->B) & 15) == 0);
   if (d->a_transposed) SFRON_CHECK_ARG(d->M % 8 == 0);
   if (d->b_transposed) SFRON_CHECK_ARG(d->N % 8 == 0);
+  // 2 GiB rule: the pipelined tiles read A and B through buffer resources with 32-bit byte offsets under a 2^31 - 1 bound (the outputs,
+  // aux and resid are addressed with size_t row offsets and carry no such limit)
+  SFRON_CHECK_ARG(sfron_fits31(d->a_transposed ? sfron_extent(d->K, d->lda, d->M, 2) : sfron_extent(d->M, d->lda, d->K, 2)) &&
+                  sfron_fits31(d->b_transposed ? sfron_extent(d->K, d->ldb, d->N, 2) : sfron_extent(d->N, d->ldb, d->K, 2)));
   GemmArgs g{};
   g.A = (const __bf16*)d->A; g.B = (const __bf16*)d->B;
   g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb;

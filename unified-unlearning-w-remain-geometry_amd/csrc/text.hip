@@ -146,6 +146,7 @@ extern "C" {
 int sfron_clip_embed(const int64_t* ids, int B, int T, const float* tok_emb, int vocab, const float* pos_emb, int D, float* out, int* err,
                      void* stream) {
   SFRON_CHECK_ARG(ids && tok_emb && pos_emb && out && err && B > 0 && T > 0 && vocab > 0 && D > 0);
+  SFRON_CHECK_ARG((int64_t)B * T < (1ll << 31));        // the row count is an `int`; the kernel's offsets are 64-bit (no byte limit)
   const int rows = B * T;
   hipLaunchKernelGGL(k_clip_embed, dim3(cdiv(rows, TPB_ROWS / WAVE)), dim3(TPB_ROWS), 0, (hipStream_t)stream, ids, rows, T, tok_emb, vocab,
                      pos_emb, D, out, err);
@@ -154,7 +155,7 @@ int sfron_clip_embed(const int64_t* ids, int B, int T, const float* tok_emb, int
 }
 
 int sfron_attn_causal_fwd(const uint16_t* qkv, uint16_t* o, int B, int T, int H, int hd, void* stream) {
-  SFRON_CHECK_ARG(qkv && o && B > 0 && H > 0);
+  SFRON_CHECK_ARG(qkv && o && B > 0 && H > 0 && (int64_t)B * H < (1ll << 31));      // grid; offsets in the kernel are size_t (no byte limit)
   if (hd != CA_HD || T < 1 || T > CA_TMAX) return SFRON_ERR_UNSUPPORTED;
   SFRON_CHECK_ARG((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)o) & 7) == 0);
   hipLaunchKernelGGL(k_attn_causal, dim3(B * H), dim3(512), 0, (hipStream_t)stream, (const __bf16*)qkv, (__bf16*)o, T, H,

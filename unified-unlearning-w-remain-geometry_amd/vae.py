@@ -14,9 +14,11 @@ conv_out), then fp32 NCHW images or the uint8 bytes of save_image / diffusers (s
 -- what DiT/forget.py:114-145 and SD/eval-scripts/generate-images.py:181-192 run through ``vae.decode``.
 
 Chunk invariant: the products take their operands through buffer resources sized by a 32-bit byte count (k_cgemm, conv.hip) and an
-``int`` row count, so an operand of 2 GiB or more is read WRONG, silently.  A batch is therefore run in chunks of samples whose largest
-operand stays under ``max_chunk_bytes`` (default 1 GiB: 32 images at 256 px, 8 at 512 px for the encoder; 16 and 4 for the decoder,
-whose largest operand is the 256-channel level after the last upsample), and every launch asserts its operands are below 2 GiB.
+``int`` row count, so the library REFUSES an operand of 2 GiB or more (sfron_conv_fwd, sfron_conv_wgrad, sfron_bgemm_bf16, sfron_gemm_bf16
+and the GroupNorm launchers return SFRON_ERR_ARG before any launch; DESIGN.md section 7 lists every entry point and its verdict).  A batch is
+therefore run in chunks of samples whose largest operand stays under ``max_chunk_bytes`` (default 1 GiB: 32 images at 256 px, 8 at 512 px
+for the encoder; 16 and 4 for the decoder, whose largest operand is the 256-channel level after the last upsample), and every launch
+asserts its operands are below 2 GiB, so the caller sees which tensor is too large rather than a status code.
 """
 import ctypes
 import json
