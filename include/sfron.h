@@ -160,6 +160,12 @@ int sfron_ddpm_loss_bwd(const float* e, const float* model_out, const float* coe
  * x0_pred = (x - eps*s1)/s2, x_next = s3*x0_pred + c1*noise + c2*eps; noise may be NULL when c1 == 0, x0_pred may be NULL */
 int sfron_ddim_step(const float* x, const float* eps, const float* noise, int64_t n, float s1, float s2, float s3, float c1,
                     float c2, float* x_next, float* x0_pred, void* stream);
+/* classifier-free guidance + one DDIM update of SD/ldm/models/diffusion/ddim.py:326-372 in one pass, fp32, in the reference's order:
+ * e = eps_uncond + guidance*(eps_cond - eps_uncond) (eps_cond NULL: e = eps_uncond); pred_x0 = (x - sqrt_one_minus_at*e)/sqrt_at;
+ * x_prev = (sqrt_a_prev*pred_x0 + dir_coef*e) + sigma*noise.  noise may be NULL when sigma == 0, pred_x0 may be NULL, x_prev may be x. */
+int sfron_ddim_cfg_step(const float* x, const float* eps_uncond, const float* eps_cond, const float* noise, int64_t n, float guidance,
+                        float sqrt_one_minus_at, float sqrt_at, float sqrt_a_prev, float dir_coef, float sigma, float* x_prev, float* pred_x0,
+                        void* stream);
 
 /* ------------------------------------------------------------------ bf16 MFMA GEMM (gemm.hip)
  * C[M,N] = alpha * op(A)[M,K] · op(B)[K,N] (+ bias[N]) with a fused epilogue; fp32 accumulation.
@@ -868,6 +874,13 @@ int sfron_clip_embed(const int64_t* ids, int B, int T, const float* tok_emb, int
  * o bf16 [B*T][H*hd]); key j > query i is masked.  T <= 128 and hd == 64 only (else SFRON_ERR_UNSUPPORTED); one workgroup per (sample, head).
  * qkv 16-byte, o 8-byte aligned.  Rows at or beyond T are neither read nor written. */
 int sfron_attn_causal_fwd(const uint16_t* qkv, uint16_t* o, int B, int T, int H, int hd, void* stream);
+/* fused cross-attention forward (csrc/xattn.hip; inference: nothing is kept for a backward pass): o = softmax(scale q k^T) v per (sample,
+ * head), bf16 operands as the batched products of the UNet take them: q [B*N][ldq], k / v [B*Lk][ldk / ldv], o [B*N][ldo], head h in
+ * columns h*hd .. h*hd + hd - 1.  Keys Lv <= j < Lk are padding with probability 0 (their rows are never read).  hd 40 / 80 / 160,
+ * 1 <= Lv <= Lk <= 128, Lk % 8 == 0, any N >= 1 (else SFRON_ERR_UNSUPPORTED).  q / k / v 16-byte aligned with leading dimensions that are
+ * multiples of 8, o 8-byte aligned with ldo % 4 == 0.  No scores or probabilities reach global memory; offsets are 64-bit. */
+int sfron_xattn_fwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo, int B, int N,
+                    int Lk, int Lv, int H, int hd, float scale, void* stream);
 /* y fp32 [rows][D] = LayerNorm(x; eps) * gamma + beta (the final LayerNorm: last_hidden_state is fp32) */
 int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, float* y, void* stream);
 

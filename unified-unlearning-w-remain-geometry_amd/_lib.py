@@ -296,6 +296,13 @@ _PROTOS.update({
 })
 
 
+_PROTOS.update({
+    "sfron_xattn_fwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _S]),
+    "sfron_ddim_cfg_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, _P, _P, _S]),
+})
+ERR_UNSUPPORTED = 1002          # SFRON_ERR_UNSUPPORTED (csrc/common.h)
+
+
 class WprepItem(ctypes.Structure):        # sfron_wprep_item
     _fields_ = [("w", c_void_p), ("fwd", c_void_p), ("dgr", c_void_p), ("co", ctypes.c_int32), ("ci", ctypes.c_int32), ("co_p", ctypes.c_int32),
                 ("ci_p", ctypes.c_int32), ("tile0", ctypes.c_int32), ("pad_", ctypes.c_int32)]

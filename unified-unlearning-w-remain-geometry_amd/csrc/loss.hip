@@ -260,6 +260,24 @@ __global__ __launch_bounds__(TPB) void k_ddim_step(const float* __restrict__ x, 
   }
 }
 
+// Classifier-free guidance + the DDIM update of ldm/models/diffusion/ddim.py p_sample_ddim in one pass, in the reference's fp32 order
+// (the file is built with -ffp-contract=off: no product is fused into a sum):
+//   e = eu + g (ec - eu)   (ec == NULL: e = eu);   pred = (x - s1 e) / s2;   x_prev = (s3 pred + dir e) + sigma noise
+// x_prev may be x: every element is read before it is written, by the same thread.
+__global__ __launch_bounds__(TPB) void k_ddim_cfg_step(const float* x, const float* __restrict__ eu, const float* __restrict__ ec,
+                                                       const float* __restrict__ noise, long n, float g, float s1, float s2, float s3, float dir,
+                                                       float sigma, float* x_prev, float* __restrict__ pred_x0) {
+  for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
+    float e = eu[i];
+    if (ec) e = e + g * (ec[i] - e);
+    const float pred = (x[i] - s1 * e) / s2;
+    float xp = s3 * pred + dir * e;
+    if (noise) xp = xp + sigma * noise[i];
+    x_prev[i] = xp;
+    if (pred_x0) pred_x0[i] = pred;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -357,6 +375,18 @@ int sfron_ddim_step(const float* x, const float* eps, const float* noise, int64_
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(k_ddim_step, dim3((int)gx), dim3(TPB), 0, (hipStream_t)stream, x, eps, noise, (long)n, s1, s2, s3, c1, c2, x_next,
                      x0_pred);
+  SFRON_LAUNCH_STATUS();
+  return SFRON_OK;
+}
+
+int sfron_ddim_cfg_step(const float* x, const float* eps_uncond, const float* eps_cond, const float* noise, int64_t n, float guidance,
+                        float sqrt_one_minus_at, float sqrt_at, float sqrt_a_prev, float dir_coef, float sigma, float* x_prev, float* pred_x0,
+                        void* stream) {
+  SFRON_CHECK_ARG(x && eps_uncond && x_prev && n > 0 && sqrt_at != 0.0f && (noise || sigma == 0.0f));
+  long gx = (n + TPB - 1) / TPB;                       // 64-bit element index in the kernel: no byte limit
+  if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(k_ddim_cfg_step, dim3((int)gx), dim3(TPB), 0, (hipStream_t)stream, x, eps_uncond, eps_cond, noise, (long)n, guidance,
+                     sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma, x_prev, pred_x0);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

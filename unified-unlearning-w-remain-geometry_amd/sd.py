@@ -29,6 +29,9 @@ class LDMSchedule:
         tab[:, 0] = np.sqrt(ac).astype(np.float32)
         tab[:, 1] = np.sqrt(1.0 - ac).astype(np.float32)
         self.tab = torch.from_numpy(tab).to(device).contiguous()
+        # the fp32 buffers register_schedule keeps (ddpm.py:184-188: torch.tensor(fp64 table, dtype=float32)); the DDIM sampler reads them
+        f32 = lambda a: torch.tensor(a, dtype=torch.float32).to(device)
+        self.betas, self.alphas_cumprod, self.alphas_cumprod_prev = f32(betas), f32(ac), f32(np.append(1.0, ac[:-1]))
 
     def q_sample(self, x_start, t, noise):
         x_start, noise = x_start.contiguous(), noise.contiguous()
@@ -63,7 +66,13 @@ class LatentDiffusion:
         self.cond_stage_model = cond_stage_model
         self.schedule = schedule or LDMSchedule(device=unet.device_)
         self.num_timesteps = self.schedule.num_timesteps
+        self.device = unet.device_
         self.training = True
+
+    # the fp32 schedule buffers of ldm's LatentDiffusion (read by sfron.ddim.DDIMSampler), taken from the schedule when asked for
+    betas = property(lambda self: self.schedule.betas)
+    alphas_cumprod = property(lambda self: self.schedule.alphas_cumprod)
+    alphas_cumprod_prev = property(lambda self: self.schedule.alphas_cumprod_prev)
 
     def train(self, mode=True):
         self.training = bool(mode)
@@ -223,3 +232,75 @@ class SDSFRon:
         self.opt.step(max_norm=None, use_mask=True)                       # :170
         u.weights_updated(convs=self.train_method == "full")
         return {"forget_loss": ori_forget, "remain_loss": ori_remain}
+
+
+@torch.no_grad()
+def sample_model(model, sampler, c, h, w, ddim_steps, scale, ddim_eta, start_code=None, n_samples=1, t_start=-1, log_every_t=None,
+                 till_T=None, verbose=True):
+    """SD/train-scripts/train-esd.py:43-84: DDIM-sample ``n_samples`` latents of an h x w image under the conditioning ``c`` with
+    guidance ``scale`` (the empty prompt is encoded through ``model.get_learned_conditioning`` when scale != 1).  Returns the latents,
+    or (latents, intermediates) when ``log_every_t`` is given.  ``sampler``: a sfron.ddim.DDIMSampler over ``model``."""
+    uc = None
+    if scale != 1.0:
+        uc = model.get_learned_conditioning(n_samples * [""])
+    log_t = 100 if log_every_t is None else log_every_t
+    shape = [4, h // 8, w // 8]
+    samples_ddim, inters = sampler.sample(S=ddim_steps, conditioning=c, batch_size=n_samples, shape=shape, verbose=False, x_T=start_code,
+                                          unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=ddim_eta,
+                                          verbose_iter=verbose, t_start=t_start, log_every_t=log_t, till_T=till_T)
+    if log_every_t is not None:
+        return samples_ddim, inters
+    return samples_ddim
+
+
+def decode_images_u8(model, z):
+    """uint8 [B, H, W, 3] on the device: ``model.decode_first_stage(z)`` as the bytes SD/eval-scripts/generate-images.py writes,
+    ``(image / 2 + 0.5).clamp(0, 1) * 255`` rounded (sfron_rows_to_image_u8, SFRON_IMAGE_ROUND)."""
+    from .images import image_mode
+    img = model.decode_first_stage(z).contiguous()              # fp32 [B, 3, H, W] in about [-1, 1]
+    B, _, H, W = img.shape
+    px = torch.empty(B * H * W, 4, dtype=torch.float32, device=img.device)
+    u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=img.device)
+    L = _lib.lib()
+    check(L.sfron_nchw_to_rows_f32(ptr(img), B, 3, H * W, 4, ptr(px), stream_ptr()), "nchw_to_rows_f32")
+    check(L.sfron_rows_to_image_u8(ptr(px), 4, B, H, W, image_mode("round"), -1.0, 1.0, 0, 0, 0, B, ptr(u8), stream_ptr()), "rows_to_image_u8")
+    return u8
+
+
+@torch.no_grad()
+def generate_images(model, prompts_path, save_path, guidance_scale=7.5, image_size=512, ddim_steps=100, num_samples=10, from_case=0,
+                    rounds=10, sampler=None):
+    """The driver loop of SD/eval-scripts/generate-images.py over the native models: for every row of the CSV at ``prompts_path``
+    (columns ``case_number``, ``prompt``, ``evaluation_seed``; rows with case_number < from_case are skipped) ``torch.manual_seed(seed)``
+    once, then ``rounds`` batches (the script's fixed 10) of ``num_samples`` start latents drawn on the CPU from that generator, each
+    sampled with guidance and decoded through ``model.decode_first_stage`` to ``<save_path>/<case>_<k>.png``, k = round * 10 + sample
+    as in the script.  Bytes are the script's ``(image / 2 + 0.5).clamp(0, 1) * 255`` rounded, through sfron_rows_to_image_u8.
+
+    The reference script steps its latents with diffusers' LMSDiscreteScheduler.  diffusers is not part of this project's environment,
+    so that scheduler cannot be pinned by a fixture and is out of scope: this driver samples with the ldm DDIM sampler (sfron.ddim,
+    eta 0), the one the reference's training scripts use.  ``model``: a LatentDiffusion with a text encoder and a VAE decoder attached.
+    Returns the list of paths written."""
+    import csv
+    import os
+    from . import ddim, images
+    sampler = sampler or ddim.DDIMSampler(model)
+    os.makedirs(save_path, exist_ok=True)
+    written = []
+    with open(prompts_path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    for row in rows:
+        case_number, seed = int(row["case_number"]), int(row["evaluation_seed"])
+        if case_number < from_case:
+            continue
+        prompt = [str(row["prompt"])] * num_samples
+        generator = torch.manual_seed(seed)                 # the global CPU generator, seeded once per prompt
+        for i in range(rounds):
+            c = model.get_learned_conditioning(prompt)
+            latents = torch.randn((num_samples, 4, image_size // 8, image_size // 8), generator=generator).to(model.device)
+            z = sample_model(model, sampler, c, image_size, image_size, ddim_steps, guidance_scale, 0.0, start_code=latents,
+                             n_samples=num_samples, verbose=False)
+            u8 = decode_images_u8(model, z)
+            B = u8.shape[0]
+            for num in range(B):
+                written.append(images.write_png(u8[num], os.path.join(save_path, f"{case_number}_{i * 10 + num}.png")))
+    return written

@@ -26,6 +26,15 @@ from ._lib import check, ptr, stream_ptr
 from .unet import Act, _TapeNet, _L, _pad8, bgemm, cast_rows, count_flops
 
 
+class PreparedContext:
+    """What UNetModel.prepare_context keeps of a context for a sampling loop: its shape and, per transformer block, the [B*Lp][2C] bf16
+    ``attn2`` key / value rows.  Only ``forward`` under ``torch.no_grad()`` takes it, for a batch of the same size; it holds products of
+    the weights as they were when it was made, so it is built per sampling call and never kept across a weight update."""
+
+    def __init__(self, model, B, Lv, Lp, kv):
+        self.model, self.B, self.Lv, self.Lp, self.kv = model, B, Lv, Lp, kv
+
+
 class UNetModel(_TapeNet):
     GN_EPS = 1e-5                                    # GroupNorm32 (util.py:225-242); SpatialTransformer.norm passes 1e-6
     RES_NAMES = (".in_layers.0", ".in_layers.2", ".out_layers.0", ".out_layers.3", ".skip_connection")
@@ -45,6 +54,7 @@ class UNetModel(_TapeNet):
         self.num_res_blocks, self.attn_res, self.channel_mult = num_res_blocks, tuple(attention_resolutions), tuple(channel_mult)
         self.heads, self.ctx_dim, self.ted = num_heads, context_dim, model_channels * 4
         self.dropout_p = 0.0
+        self.fused_cross_attention = False           # opt-in (sfron.ddim sets it): no-grad forwards run attn2 on sfron_xattn_fwd
         self._plan()
         self._alloc()
         self._register_views()
@@ -234,8 +244,62 @@ class UNetModel(_TapeNet):
             check(_L().sfron_attn_bwd(ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(delta), dq, B, N, h, d, stream_ptr()), "attn_bwd")
         return O, bwd
 
-    def _transformer(self, tape, name, x, ctx, Lp, Lv):
-        """SpatialTransformer with one BasicTransformerBlock; ctx bf16 [B*Lp][ctx_dim] (rows >= Lv are zero)."""
+    def _pad_context(self, context):
+        """[B][Lv][ctx] -> bf16 rows padded to a multiple of 8 tokens (zero rows: zero keys / values, probability 0)"""
+        B, Lv = context.shape[0], context.shape[1]
+        Lp = _pad8(Lv)
+        ctx = torch.zeros(B * Lp, self.ctx_dim, dtype=torch.bfloat16, device=self.device_)
+        ctx.view(B, Lp, self.ctx_dim)[:, :Lv].copy_(context)
+        return ctx, Lp, Lv
+
+    def _context_kv(self, name, ctx, rows):
+        """attn2's keys and values of one transformer block: [rows][2C] bf16 = ctx [to_k ; to_v]^T"""
+        C = dict(self.st_blocks)[name]
+        kv = torch.empty(rows, 2 * C, dtype=torch.bfloat16, device=self.device_)
+        bgemm(ctx, self._w(name + ".transformer_blocks.0.attn2.to_k.weight"), rows, 2 * C, self.ctx_dim, lda=self.ctx_dim, ldb=self.ctx_dim,
+              c_bf16=kv, ldc=2 * C)
+        return kv
+
+    def prepare_context(self, context):
+        """Pads and casts ``context`` [B][Lv][ctx] once and runs every block's attn2 key / value GEMM once: the 16 GEMMs a sampling loop
+        would otherwise repeat on every step over a context that does not change.  Inference only (``torch.no_grad()``)."""
+        assert not torch.is_grad_enabled(), "prepare_context is for inference: call it under torch.no_grad()"
+        ctx, Lp, Lv = self._pad_context(context)
+        B = context.shape[0]
+        return PreparedContext(self, B, Lv, Lp, {n: self._context_kv(n, ctx, B * Lp) for n, _ in self.st_blocks})
+
+    def per_sample_bytes(self, H, W):
+        """The widest operand one sample of an H x W latent puts into a launch of the forward pass: per attention level the fp32 GEGLU
+        projection [HW][8C], the fp32 scores of a self-attention that takes _mha ([h][HW][HW]), and the concatenated skip input of the
+        first output block of a level ([HW][2C] fp32 at most 3C wide).  The sampler sizes its batch chunks by it."""
+        big, ds = 0, 1
+        for level, mult in enumerate(self.channel_mult):
+            C, N = mult * self.mc, (H // ds) * (W // ds)
+            big = max(big, N * 3 * C * 4)
+            if ds in self.attn_res:
+                big = max(big, N * 8 * C * 4)
+                d = C // self.heads
+                if not (d <= 80 and d % 8 == 0 and N % 64 == 0):
+                    big = max(big, self.heads * N * N * 4)
+            if level != len(self.channel_mult) - 1:
+                ds *= 2
+        return big
+
+    def _fused_cross_attention(self, q2, kv, B, N, Lp, Lv, C):
+        """attn2 on sfron_xattn_fwd (scores stay on the chip); None where the kernel does not take the shape (the caller keeps _mha)."""
+        d = C // self.heads
+        O = torch.empty(B * N, C, dtype=torch.bfloat16, device=self.device_)
+        st = _L().sfron_xattn_fwd(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, O.data_ptr(), C, B, N, Lp, Lv, self.heads, d,
+                                  float(d ** -0.5), stream_ptr())
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        check(st, "xattn_fwd")
+        count_flops(4.0 * N * Lp * d * self.heads * B)
+        return O
+
+    def _transformer(self, tape, name, x, ctx, Lp, Lv, kv=None, fused=False):
+        """SpatialTransformer with one BasicTransformerBlock; ctx bf16 [B*Lp][ctx_dim] (rows >= Lv are zero).  kv: this block's rows of a
+        PreparedContext (ctx is then None); fused: cross-attention on sfron_xattn_fwd (both forward-only)."""
         dev, B, C, N = self.device_, x.B, x.C, x.H * x.W
         rows, t = x.rows, name + ".transformer_blocks.0"
         hn, gn_b = self._gn(tape, x, name + ".norm", False, eps=1e-6)
@@ -256,9 +320,12 @@ class UNetModel(_TapeNet):
         n2, ln2_b = self._layernorm(X1, t + ".norm2")
         q2 = torch.empty(rows, C, dtype=torch.bfloat16, device=dev)
         bgemm(n2, self._w(t + ".attn2.to_q.weight"), rows, C, C, lda=C, ldb=C, c_bf16=q2, ldc=C)
-        kv = torch.empty(B * Lp, 2 * C, dtype=torch.bfloat16, device=dev)
-        bgemm(ctx, self._w(t + ".attn2.to_k.weight"), B * Lp, 2 * C, self.ctx_dim, lda=self.ctx_dim, ldb=self.ctx_dim, c_bf16=kv, ldc=2 * C)
-        O2, att2_b = self._mha(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, B, N, Lp, Lv, C, keep=(q2, kv))
+        if kv is None:
+            kv = self._context_kv(name, ctx, B * Lp)
+        O2 = self._fused_cross_attention(q2, kv, B, N, Lp, Lv, C) if fused else None
+        att2_b = None                                                   # the fused form is forward-only
+        if O2 is None:
+            O2, att2_b = self._mha(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, B, N, Lp, Lv, C, keep=(q2, kv))
         x2_t, o2_b = self._linear(O2, rows, t + ".attn2.to_out.0", C, C, resid=X1.t)
         X2 = Act(x2_t, B, x.H, x.W, C)
         # ---- GEGLU feed-forward
@@ -314,10 +381,15 @@ class UNetModel(_TapeNet):
         tape = []
         self._prep_conv_weights()
         # context: [B][Lv][ctx] -> bf16 rows padded to a multiple of 8 tokens (zero rows: zero keys / values, probability 0)
-        Lv = context.shape[1]
-        Lp = _pad8(Lv)
-        ctx = torch.zeros(B * Lp, self.ctx_dim, dtype=torch.bfloat16, device=dev)
-        ctx.view(B, Lp, self.ctx_dim)[:, :Lv].copy_(context)
+        fwd_only = not need_grad and not torch.is_grad_enabled()
+        if isinstance(context, PreparedContext):
+            assert fwd_only, "a PreparedContext is valid only under torch.no_grad()"
+            assert context.model is self and context.B == B, "the PreparedContext was made by another model or for another batch size"
+            ctx, Lp, Lv, kvs = None, context.Lp, context.Lv, context.kv
+        else:
+            ctx, Lp, Lv = self._pad_context(context)
+            kvs = None
+        tkw = lambda n: dict(kv=None if kvs is None else kvs[n], fused=bool(self.fused_cross_attention) and fwd_only)
         # ---- time embedding (:817-818): emb = Linear(SiLU(Linear(timestep_embedding(t))))
         te = torch.empty(B, mc, dtype=torch.bfloat16, device=dev)
         check(L.sfron_timestep_embed(ptr(timesteps.to(torch.int64).contiguous()), B, mc, ptr(te), mc, stream_ptr()), "timestep_embed")
@@ -346,7 +418,7 @@ class UNetModel(_TapeNet):
                 cin, cout = res_c[n0]
                 h = self._resblock(tape, n0, hs[-1], cin, cout, proj, d_proj, None)
                 if n1:
-                    h = self._transformer(tape, n1, h, ctx, Lp, Lv)
+                    h = self._transformer(tape, n1, h, ctx, Lp, Lv, **tkw(n1))
                 hs.append(h)
             else:
                 src = hs[-1]
@@ -364,7 +436,7 @@ class UNetModel(_TapeNet):
         # ---- middle
         C = self.mid_c
         h = self._resblock(tape, "middle_block.0", hs[-1], C, C, proj, d_proj, None)
-        h = self._transformer(tape, "middle_block.1", h, ctx, Lp, Lv)
+        h = self._transformer(tape, "middle_block.1", h, ctx, Lp, Lv, **tkw("middle_block.1"))
         h = self._resblock(tape, "middle_block.2", h, C, C, proj, d_proj, None)
         # ---- output blocks
         for n0, att, up in self.outp:
@@ -384,7 +456,7 @@ class UNetModel(_TapeNet):
             tape.append(cat_bwd)
             h = self._resblock(tape, n0, ca, cin, cout, proj, d_proj, None)
             if att:
-                h = self._transformer(tape, att, h, ctx, Lp, Lv)
+                h = self._transformer(tape, att, h, ctx, Lp, Lv, **tkw(att))
             if up:
                 src = h
                 sb = cast_rows(src.t, src.C, src.rows, src.C, dev)
