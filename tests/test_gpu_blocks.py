@@ -133,7 +133,8 @@ def test_conditioning_and_layout():
     close(ops.unpatchify(r2.float(), 2, 8, 8, 8, 2), im8.to(torch.bfloat16).float(), 0, 0)
 
 
-@pytest.mark.parametrize("B,T,H,hd", [(2, 256, 16, 72), (1, 128, 3, 72), (1, 256, 4, 64), (1, 1024, 8, 40), (2, 256, 4, 80), (1, 384, 2, 48), (3, 512, 2, 40)])
+@pytest.mark.parametrize("B,T,H,hd", [(2, 256, 16, 72), (1, 128, 3, 72), (1, 256, 4, 64), (1, 1024, 8, 40), (2, 256, 4, 80), (1, 384, 2, 48), (3, 512, 2, 40),
+                                      (2, 256, 3, 8), (2, 256, 3, 24), (2, 256, 3, 56)])
 def test_attention_forward_eight_wave_form_is_bit_identical(B, T, H, hd):
     """k_attn_fwd8 (round 4: eight waves of 16 query rows per workgroup, sixteen waves per CU) and the whole-head form (eight waves of 32
     rows: form 16, taken where the sequence is a multiple of 256 rows) against the four-wave kernel: the same products and the same softmax
