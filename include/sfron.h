@@ -881,6 +881,24 @@ int sfron_attn_causal_fwd(const uint16_t* qkv, uint16_t* o, int B, int T, int H,
  * multiples of 8, o 8-byte aligned with ldo % 4 == 0.  No scores or probabilities reach global memory; offsets are 64-bit. */
 int sfron_xattn_fwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo, int B, int N,
                     int Lk, int Lv, int H, int hd, float scale, void* stream);
+/* sfron_xattn_fwd for training: the same kernel (o is bit-identical) with one more store per query row, lse fp32 [B*H*N],
+ * lse[(b*H + h)*N + n] = m + log(l) = log sum_j exp(scale q_n . k_j) over the keys j < Lv -- what sfron_xattn_bwd rebuilds P from. */
+int sfron_xattn_fwd_lse(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo, int B, int N,
+                        int Lk, int Lv, int H, int hd, float scale, float* lse, void* stream);
+/* fused cross-attention backward (csrc/xattn.hip), shapes and layouts of sfron_xattn_fwd: with P = exp(scale q k^T - lse) (keys >= Lv: 0),
+ * delta = rowsum(d_o o o), dP = d_o v^T and dS = scale P o (dP - delta):  dq [B*N][lddq] = dS k,  dk [B*Lk][lddk] = dS^T q,
+ * dv [B*Lk][lddv] = P^T d_o (bf16, head h in columns h*hd ..; the layouts the batched products of UNetModel._mha write).  P and dS are
+ * rounded to bf16 as MFMA operands, sums are fp32, outputs are rounded once; no score-sized matrix reaches global memory.  Rows Lv .. Lk-1
+ * of dk / dv are written as exact zeros and those rows of k / v are never read; rows of dq at or beyond B*N and columns at or beyond H*hd
+ * of any output are not touched.  dk / dv are summed over the queries in a fixed order (fp32 partial slabs in ws, one per chunk of 64-row
+ * query tiles, then a finishing kernel that adds them in chunk order): no atomics, two calls give the same bits.
+ * ws: caller-owned, 16-byte aligned, at least sfron_xattn_bwd_ws_bytes(B, N, Lk, H, hd) bytes, contents undefined before and after.
+ * q / k / v / o / d_o 16-byte aligned with leading dimensions % 8 == 0; dq / dk / dv 8-byte aligned with leading dimensions % 4 == 0.
+ * Unsupported hd / Lk: SFRON_ERR_UNSUPPORTED; anything else wrong (ws too small included): SFRON_ERR_ARG; both before any launch. */
+int64_t sfron_xattn_bwd_ws_bytes(int B, int N, int Lk, int H, int hd);
+int sfron_xattn_bwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, const uint16_t* o, int ldo,
+                    const uint16_t* d_o, int ldd_o, const float* lse, uint16_t* dq, int lddq, uint16_t* dk, int lddk, uint16_t* dv, int lddv, int B,
+                    int N, int Lk, int Lv, int H, int hd, float scale, void* ws, int64_t ws_bytes, void* stream);
 /* y fp32 [rows][D] = LayerNorm(x; eps) * gamma + beta (the final LayerNorm: last_hidden_state is fp32) */
 int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, float* y, void* stream);
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 4 on the HIP path: SD v1 UNet nsfw_removal SFR-on iterations/s (batch 2, 64x64 latents, 77-token context).
-    python tools/bench_sd.py [--steps 5] [--batch 2] [--method full|xattn]"""
+    python tools/bench_sd.py [--steps 5] [--batch 2] [--method full|xattn]
+    python tools/bench_sd.py --fused-xattn [--batch 8] [--steps 5]     both train methods, SDSFRon(fused_xattn=False) and (fused_xattn=True) taking turns
+                                                                      in one process, five rounds: minimum and spread of each"""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -8,6 +10,7 @@ import torch
 ap = argparse.ArgumentParser(); ap.add_argument("--steps", type=int, default=5); ap.add_argument("--batch", type=int, default=2)
 ap.add_argument("--method", default="full")
 ap.add_argument("--eager", action="store_true", help="no HIP-graph replay of the stages")
+ap.add_argument("--fused-xattn", action="store_true", help="A-B of the fused differentiable cross-attention (flag off = the default path)")
 a = ap.parse_args()
 from sfron import sd, sd_unet
 if os.environ.get("SFRON_FUSE_SPLIT_FINISH"):       # A-B knob: 0 = every split convolution finishes its own output (before round 6, late)
@@ -25,8 +28,7 @@ with torch.no_grad():
         if not bool(p.any()):
             p.copy_((torch.randn(p.shape, generator=g) * 0.02).to(p.device))
 model.sync_bf16()
-run = sd.SDSFRon(model, lr=1e-5, train_method=a.method, use_graphs=not a.eager)
-B = a.batch
+B = a.batch if not (a.fused_xattn and a.batch == 2) else 8
 gd = torch.Generator(device=DEV).manual_seed(2)
 rn = lambda *s: torch.randn(*s, device=DEV, generator=gd)
 c_f, c_p = rn(1, 77, 768).expand(B, -1, -1).contiguous(), rn(1, 77, 768).expand(B, -1, -1).contiguous()
@@ -35,6 +37,28 @@ def batch():
     return (dict(x_f=xf, x_p=xf, c_f=c_f, c_p=c_p, t=torch.randint(0, 1000, (B,), device=DEV, generator=gd), noise=rn(B, 4, 64, 64)),
             dict(x=rn(B, 4, 64, 64), c=c_p, t=torch.randint(0, 1000, (B,), device=DEV, generator=gd), noise=rn(B, 4, 64, 64)))
 bts = [batch() for _ in range(2)]
+if a.fused_xattn:
+    # one model, one runner per mode (each with its own graphs); the switch is read when a stage is run eagerly or captured
+    for method in ("full", "xattn"):
+        runs = {}
+        for on in (False, True):
+            model.fused_cross_attention_train = False
+            runs[on] = sd.SDSFRon(model, lr=1e-5, train_method=method, use_graphs=not a.eager, fused_xattn=on)
+        times = {False: [], True: []}
+        for rnd in range(6):                           # round 0 warms up (and captures)
+            for on in (False, True):
+                model.fused_cross_attention_train = on
+                torch.cuda.synchronize(); t0 = time.time()
+                for i in range(a.steps): runs[on].step(*bts[i % 2])
+                torch.cuda.synchronize()
+                if rnd:
+                    times[on].append((time.time() - t0) / a.steps * 1e3)
+        off, on = times[False], times[True]
+        print(f"SD v1 SFR-on iteration, batch {B}, train_method {method}: flag off min {min(off):.1f} ms (spread {max(off) - min(off):.1f}), "
+              f"fused_xattn min {min(on):.1f} ms (spread {max(on) - min(on):.1f}), difference {min(on) - min(off):+.1f} ms")
+        del runs
+    sys.exit(0)
+run = sd.SDSFRon(model, lr=1e-5, train_method=a.method, use_graphs=not a.eager)
 for i in range(2): run.step(*bts[i % 2])
 torch.cuda.synchronize(); t0 = time.time()
 for i in range(a.steps): run.step(*bts[i % 2])

@@ -120,7 +120,9 @@ class LatentDiffusion:
 
 class SDSFRon:
     def __init__(self, unet, schedule=None, lr=1e-5, forget_alpha=1.0, remain_alpha=1.0, train_method="full", mask=None,
-                 mask_mode="as_written", process_group=None, use_graphs=False):
+                 mask_mode="as_written", process_group=None, use_graphs=False, fused_xattn=False):
+        """fused_xattn: run the UNet's cross-attention on the fused differentiable kernels (UNetModel.fused_cross_attention_train): scores and
+        probabilities stay on the chip in the forward and the backward passes; opt-in, the default launches are unchanged."""
         from . import dp
         self.use_graphs, self._graphs, self._pool = bool(use_graphs), {}, (graphs.shared_pool() if use_graphs else None)
         if train_method not in ("full", "xattn"):
@@ -166,6 +168,8 @@ class SDSFRon:
         self.opt = sweep.FlatAdam(p, g, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adamw=True, mask=self.train_mask, w_bf16=w16,
                                   ranges=ranges)
         unet.auto_prep = False                      # this loop tells the model when its weights changed
+        if fused_xattn:
+            unet.fused_cross_attention_train = True
         unet.wgrad_filter = (lambda n: "attn2" in n) if train_method == "xattn" else None
 
     def _d_loss(self, out, target, scale):

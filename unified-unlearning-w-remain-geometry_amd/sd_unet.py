@@ -55,6 +55,9 @@ class UNetModel(_TapeNet):
         self.heads, self.ctx_dim, self.ted = num_heads, context_dim, model_channels * 4
         self.dropout_p = 0.0
         self.fused_cross_attention = False           # opt-in (sfron.ddim sets it): no-grad forwards run attn2 on sfron_xattn_fwd
+        # opt-in (SDSFRon(fused_xattn=True)): passes that keep a tape run attn2 on sfron_xattn_fwd_lse + sfron_xattn_bwd, passes that keep
+        # none (need_grad=False, the stop-gradient branch under enabled grad mode included) on sfron_xattn_fwd
+        self.fused_cross_attention_train = False
         self._plan()
         self._alloc()
         self._register_views()
@@ -297,9 +300,36 @@ class UNetModel(_TapeNet):
         count_flops(4.0 * N * Lp * d * self.heads * B)
         return O
 
-    def _transformer(self, tape, name, x, ctx, Lp, Lv, kv=None, fused=False):
+    def _fused_cross_attention_train(self, q2, kv, B, N, Lp, Lv, C):
+        """attn2 on sfron_xattn_fwd_lse, with a backward closure on sfron_xattn_bwd in _mha's calling convention; None where the kernels do
+        not take the shape (the caller keeps _mha).  The tape holds q2, kv, O and the row statistic lse [B*h*N] fp32 -- no probabilities."""
+        h, dev = self.heads, self.device_
+        d = C // h
+        scale = float(d ** -0.5)
+        O = torch.empty(B * N, C, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B * h * N, dtype=torch.float32, device=dev)
+        st = _L().sfron_xattn_fwd_lse(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, O.data_ptr(), C, B, N, Lp, Lv, h, d,
+                                      scale, lse.data_ptr(), stream_ptr())
+        if st == _lib.ERR_UNSUPPORTED:
+            return None, None
+        check(st, "xattn_fwd_lse")
+        count_flops(4.0 * N * Lp * d * h * B)
+
+        def bwd(dO, dq, dk, dv):
+            # the workspace (fp32 dK / dV partial slabs) comes from torch's allocator on the current stream: a graph capture takes it from
+            # the capture's pool like every other temporary of the tape
+            nb = _L().sfron_xattn_bwd_ws_bytes(B, N, Lp, h, d)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            count_flops(8.0 * N * Lp * d * h * B)         # dP, dQ, dK, dV (the recomputed S is not algorithmic work)
+            check(_L().sfron_xattn_bwd(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, O.data_ptr(), C, ptr(dO), C,
+                                       lse.data_ptr(), dq, C, dk, 2 * C, dv, 2 * C, B, N, Lp, Lv, h, d, scale, ws.data_ptr(), nb, stream_ptr()),
+                  "xattn_bwd")
+        return O, bwd
+
+    def _transformer(self, tape, name, x, ctx, Lp, Lv, kv=None, fused=False, fused_train=False):
         """SpatialTransformer with one BasicTransformerBlock; ctx bf16 [B*Lp][ctx_dim] (rows >= Lv are zero).  kv: this block's rows of a
-        PreparedContext (ctx is then None); fused: cross-attention on sfron_xattn_fwd (both forward-only)."""
+        PreparedContext (ctx is then None); fused: cross-attention on sfron_xattn_fwd (both forward-only); fused_train: cross-attention
+        on sfron_xattn_fwd_lse with sfron_xattn_bwd on the tape."""
         dev, B, C, N = self.device_, x.B, x.C, x.H * x.W
         rows, t = x.rows, name + ".transformer_blocks.0"
         hn, gn_b = self._gn(tape, x, name + ".norm", False, eps=1e-6)
@@ -324,6 +354,8 @@ class UNetModel(_TapeNet):
             kv = self._context_kv(name, ctx, B * Lp)
         O2 = self._fused_cross_attention(q2, kv, B, N, Lp, Lv, C) if fused else None
         att2_b = None                                                   # the fused form is forward-only
+        if O2 is None and fused_train:
+            O2, att2_b = self._fused_cross_attention_train(q2, kv, B, N, Lp, Lv, C)
         if O2 is None:
             O2, att2_b = self._mha(q2.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, B, N, Lp, Lv, C, keep=(q2, kv))
         x2_t, o2_b = self._linear(O2, rows, t + ".attn2.to_out.0", C, C, resid=X1.t)
@@ -389,7 +421,10 @@ class UNetModel(_TapeNet):
         else:
             ctx, Lp, Lv = self._pad_context(context)
             kvs = None
-        tkw = lambda n: dict(kv=None if kvs is None else kvs[n], fused=bool(self.fused_cross_attention) and fwd_only)
+        train_fused = bool(self.fused_cross_attention_train)
+        tkw = lambda n: dict(kv=None if kvs is None else kvs[n],
+                             fused=(bool(self.fused_cross_attention) and fwd_only) or (train_fused and not need_grad),
+                             fused_train=train_fused and need_grad)
         # ---- time embedding (:817-818): emb = Linear(SiLU(Linear(timestep_embedding(t))))
         te = torch.empty(B, mc, dtype=torch.bfloat16, device=dev)
         check(L.sfron_timestep_embed(ptr(timesteps.to(torch.int64).contiguous()), B, mc, ptr(te), mc, stream_ptr()), "timestep_embed")
