@@ -899,6 +899,27 @@ int64_t sfron_xattn_bwd_ws_bytes(int B, int N, int Lk, int H, int hd);
 int sfron_xattn_bwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, const uint16_t* o, int ldo,
                     const uint16_t* d_o, int ldd_o, const float* lse, uint16_t* dq, int lddq, uint16_t* dk, int lddk, uint16_t* dv, int lddv, int B,
                     int N, int Lk, int Lv, int H, int hd, float scale, void* ws, int64_t ws_bytes, void* stream);
+/* fused self-attention for wide heads (csrc/wattn.hip): o = softmax(scale q k^T) v per (sample, head) over the T tokens of the sample
+ * itself, bf16 operands by address + leading dimension as sfron_xattn_fwd takes them: q / k / v / o [B*T][ld], head h in columns
+ * h*hd .. h*hd + hd - 1 (one [B*T][3*H*hd] qkv matrix serves as three column slices).  hd 160 or 256, T a multiple of 64 with
+ * 64 <= T <= 1024 -- sfron_wattn_supported(T, hd) returns 1 for exactly these -- anything else SFRON_ERR_UNSUPPORTED.  lse may be NULL
+ * (inference); otherwise fp32 [B*H*T], lse[(b*H + h)*T + t] = m + log(l) = log sum_j exp(scale q_t . k_j), what sfron_wattn_bwd rebuilds
+ * P from.  o is bit-identical with and without lse.  K / V stream through LDS in chunks of 64 keys under an fp32 online softmax; no
+ * scores or probabilities reach global memory; offsets are 64-bit.  Every pointer 16-byte aligned (lse: 4), every leading dimension a
+ * multiple of 8 and >= H*hd; a refusal (SFRON_ERR_UNSUPPORTED for the shape, SFRON_ERR_ARG for anything else) comes before any launch. */
+int sfron_wattn_supported(int T, int hd);
+int sfron_wattn_fwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo, float* lse, int B,
+                    int T, int H, int hd, float scale, void* stream);
+/* backward of sfron_wattn_fwd, same shapes and layouts: with P = exp(scale q k^T - lse), delta = rowsum(d_o o o), dP = d_o v^T and
+ * dS = scale P o (dP - delta):  dq = dS k,  dk = dS^T q,  dv = P^T d_o (bf16 [B*T][ld], head h in columns h*hd ..).  P and dS are rounded
+ * to bf16 as MFMA operands, sums are fp32, outputs are rounded once.  Two kernels: one over query tiles (delta -> ws, dq), one over key
+ * tiles (dk, dv; a workgroup owns its 64 keys and walks the queries in order): no atomics, no partial sums between workgroups, two
+ * calls give the same bits.  ws: caller-owned, 16-byte aligned, at least sfron_wattn_bwd_ws_bytes(B, T, H, hd) bytes (delta, fp32
+ * [B*H*T]), contents undefined before and after.  Refusals as sfron_wattn_fwd; a workspace that is too small is SFRON_ERR_ARG. */
+int64_t sfron_wattn_bwd_ws_bytes(int B, int T, int H, int hd);
+int sfron_wattn_bwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, const uint16_t* o, int ldo,
+                    const uint16_t* d_o, int ldd_o, const float* lse, uint16_t* dq, int lddq, uint16_t* dk, int lddk, uint16_t* dv, int lddv, int B,
+                    int T, int H, int hd, float scale, void* ws, int64_t ws_bytes, void* stream);
 /* y fp32 [rows][D] = LayerNorm(x; eps) * gamma + beta (the final LayerNorm: last_hidden_state is fp32) */
 int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, float* y, void* stream);
 

@@ -304,6 +304,13 @@ _PROTOS.update({
                                 c_int, c_int, c_int, c_float, _P, c_int64, _S]),
     "sfron_ddim_cfg_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, _P, _P, _S]),
 })
+_PROTOS.update({
+    "sfron_wattn_supported": (c_int, [c_int, c_int]),
+    "sfron_wattn_fwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_float, _S]),
+    "sfron_wattn_bwd_ws_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfron_wattn_bwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int,
+                                c_int, c_float, _P, c_int64, _S]),
+})
 ERR_UNSUPPORTED = 1002          # SFRON_ERR_UNSUPPORTED (csrc/common.h)
 
 

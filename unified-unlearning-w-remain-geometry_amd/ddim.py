@@ -53,9 +53,12 @@ def _f32(v):
 
 
 class DDIMSampler(object):
-    def __init__(self, model, schedule="linear", **kwargs):
+    def __init__(self, model, schedule="linear", fused_wide_attn=False, **kwargs):
+        """fused_wide_attn: for the duration of a sampling call the native UNet runs its wide-head self-attention (head width 160: the
+        16x16, 8x8 and middle attn1 of SD v1) on the fused kernels of csrc/wattn.hip (UNetModel.fused_wide_self_attention); off by default."""
         super().__init__()
         self.model = model
+        self.fused_wide_attn = bool(fused_wide_attn)
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule
 
@@ -109,10 +112,13 @@ class DDIMSampler(object):
             yield c_in
             return
         keep, unet.fused_cross_attention = unet.fused_cross_attention, True
+        keep_w = unet.fused_wide_self_attention
+        unet.fused_wide_self_attention = keep_w or self.fused_wide_attn
         try:
             yield unet.prepare_context(c_in)
         finally:
             unet.fused_cross_attention = keep
+            unet.fused_wide_self_attention = keep_w
 
     def chunk_size(self, batch_size, shape):
         """Samples per run such that no operand of the UNet at batch 2B reaches 2 GiB (the library refuses those); the native UNet

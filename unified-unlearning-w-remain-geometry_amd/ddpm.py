@@ -220,7 +220,9 @@ class DDPMSFRon:
 
     def __init__(self, model, betas=None, lr=1e-4, forget_alpha=10.0, remain_alpha=1.0, grad_clip=1.0, ema_rate=None, mask=None,
                  unlearn_loss="adaga", lambd=0.5, n_iters=50, decay_forget_alpha=True, cond_drop_prob=0.1, process_group=None,
-                 label_to_forget=0, n_classes=10, use_graphs=False, method="ron"):
+                 label_to_forget=0, n_classes=10, use_graphs=False, method="ron", fused_attn=False):
+        """fused_attn: run the denoiser's AttnBlocks on the fused self-attention kernels of csrc/wattn.hip
+        (Conditional_Model.fused_attention); opt-in, the default launches are unchanged."""
         from . import dp, sweep
         self.use_graphs, self._graphs, self._pool = bool(use_graphs), {}, None
         # method "joint" (runners/diffusion.py:1160-1167): ONE clipped Adam step per iteration on remain_alpha * remain_loss +
@@ -233,6 +235,10 @@ class DDPMSFRon:
             raise ValueError(f"unsupported unlearn_loss {unlearn_loss!r} (DDPM/runners/diffusion.py:1095-1120 defines ga, rl, adaga)")
         self.label_to_forget, self.n_classes = label_to_forget, n_classes
         self.model, self.flat = model, FlatParams(model)
+        if fused_attn:
+            if not hasattr(model, "fused_attention"):
+                raise ValueError("fused_attn needs the native Conditional_Model (it has no effect on another denoiser)")
+            model.fused_attention = True
         dev = self.flat.p.device
         self.b = pin_alphas_cumprod(betas if betas is not None else get_beta_schedule(device=dev))
         self.forget_alpha, self.remain_alpha, self.grad_clip = forget_alpha, remain_alpha, grad_clip

@@ -120,8 +120,10 @@ class LatentDiffusion:
 
 class SDSFRon:
     def __init__(self, unet, schedule=None, lr=1e-5, forget_alpha=1.0, remain_alpha=1.0, train_method="full", mask=None,
-                 mask_mode="as_written", process_group=None, use_graphs=False, fused_xattn=False):
-        """fused_xattn: run the UNet's cross-attention on the fused differentiable kernels (UNetModel.fused_cross_attention_train): scores and
+                 mask_mode="as_written", process_group=None, use_graphs=False, fused_xattn=False, fused_wide_attn=False):
+        """fused_wide_attn: run the UNet's self-attention of head width 160 (attn1 at the 16x16, 8x8 and middle levels) on the fused kernels of
+        csrc/wattn.hip (UNetModel.fused_wide_self_attention) instead of batched products + softmax; opt-in, off by default.
+        fused_xattn: run the UNet's cross-attention on the fused differentiable kernels (UNetModel.fused_cross_attention_train): scores and
         probabilities stay on the chip in the forward and the backward passes; opt-in, the default launches are unchanged."""
         from . import dp
         self.use_graphs, self._graphs, self._pool = bool(use_graphs), {}, (graphs.shared_pool() if use_graphs else None)
@@ -170,6 +172,8 @@ class SDSFRon:
         unet.auto_prep = False                      # this loop tells the model when its weights changed
         if fused_xattn:
             unet.fused_cross_attention_train = True
+        if fused_wide_attn:
+            unet.fused_wide_self_attention = True
         unet.wgrad_filter = (lambda n: "attn2" in n) if train_method == "xattn" else None
 
     def _d_loss(self, out, target, scale):

@@ -58,6 +58,10 @@ class UNetModel(_TapeNet):
         # opt-in (SDSFRon(fused_xattn=True)): passes that keep a tape run attn2 on sfron_xattn_fwd_lse + sfron_xattn_bwd, passes that keep
         # none (need_grad=False, the stop-gradient branch under enabled grad mode included) on sfron_xattn_fwd
         self.fused_cross_attention_train = False
+        # opt-in (SDSFRon(fused_wide_attn=True), DDIMSampler(fused_wide_attn=True)): attn1 with a head too wide for csrc/attn.hip (head
+        # width 160) tries the fused kernels of csrc/wattn.hip before _mha -- sfron_wattn_fwd + sfron_wattn_bwd where a tape is kept, the
+        # forward without lse otherwise
+        self.fused_wide_self_attention = False
         self._plan()
         self._alloc()
         self._register_views()
@@ -247,6 +251,35 @@ class UNetModel(_TapeNet):
             check(_L().sfron_attn_bwd(ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(delta), dq, B, N, h, d, stream_ptr()), "attn_bwd")
         return O, bwd
 
+    def _wide_self_attention(self, qkv, B, N, C, train):
+        """attn1 on the fused wide-head kernels of csrc/wattn.hip (qkv [B*N][3C], column = which * C + head * d + i), with a backward
+        closure in _mha's calling convention when `train`; None where the kernels do not take the shape (the caller keeps _mha).  The
+        tape holds qkv, O and lse [B*h*N] fp32 -- no probabilities."""
+        h, dev = self.heads, self.device_
+        d = C // h
+        if not _L().sfron_wattn_supported(N, d):
+            return None, None
+        scale = float(d ** -0.5)
+        q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C
+        O = torch.empty(B * N, C, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B * h * N, dtype=torch.float32, device=dev) if train else None
+        st = _L().sfron_wattn_fwd(q, 3 * C, k, 3 * C, v, 3 * C, O.data_ptr(), C, ptr(lse), B, N, h, d, scale, stream_ptr())
+        if st == _lib.ERR_UNSUPPORTED:
+            return None, None
+        check(st, "wattn_fwd")
+        count_flops(4.0 * N * N * d * h * B)
+        if not train:
+            return O, None
+
+        def bwd(dO, dq, dk, dv, _keep=qkv):
+            # the workspace (delta) comes from torch's allocator on the current stream: a graph capture takes it from the capture's pool
+            nb = _L().sfron_wattn_bwd_ws_bytes(B, N, h, d)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            count_flops(8.0 * N * N * d * h * B)          # dP, dQ, dK, dV (the recomputed S is not algorithmic work)
+            check(_L().sfron_wattn_bwd(q, 3 * C, k, 3 * C, v, 3 * C, O.data_ptr(), C, ptr(dO), C, lse.data_ptr(), dq, 3 * C, dk, 3 * C, dv, 3 * C,
+                                       B, N, h, d, scale, ws.data_ptr(), nb, stream_ptr()), "wattn_bwd")
+        return O, bwd
+
     def _pad_context(self, context):
         """[B][Lv][ctx] -> bf16 rows padded to a multiple of 8 tokens (zero rows: zero keys / values, probability 0)"""
         B, Lv = context.shape[0], context.shape[1]
@@ -326,10 +359,11 @@ class UNetModel(_TapeNet):
                   "xattn_bwd")
         return O, bwd
 
-    def _transformer(self, tape, name, x, ctx, Lp, Lv, kv=None, fused=False, fused_train=False):
+    def _transformer(self, tape, name, x, ctx, Lp, Lv, kv=None, fused=False, fused_train=False, wide=None):
         """SpatialTransformer with one BasicTransformerBlock; ctx bf16 [B*Lp][ctx_dim] (rows >= Lv are zero).  kv: this block's rows of a
         PreparedContext (ctx is then None); fused: cross-attention on sfron_xattn_fwd (both forward-only); fused_train: cross-attention
-        on sfron_xattn_fwd_lse with sfron_xattn_bwd on the tape."""
+        on sfron_xattn_fwd_lse with sfron_xattn_bwd on the tape; wide: None, or "fwd" / "train" -- an attn1 that would take _mha tries
+        the fused wide-head kernels first, without / with what the backward pass needs."""
         dev, B, C, N = self.device_, x.B, x.C, x.H * x.W
         rows, t = x.rows, name + ".transformer_blocks.0"
         hn, gn_b = self._gn(tape, x, name + ".norm", False, eps=1e-6)
@@ -343,7 +377,10 @@ class UNetModel(_TapeNet):
         if (C // self.heads) <= 80 and (C // self.heads) % 8 == 0 and N % 64 == 0:
             O1, att1_b = self._flash_self_attention(qkv, B, N, C)       # scores never leave the chip (4096 tokens at 64x64)
         else:
-            O1, att1_b = self._mha(qkv.data_ptr(), 3 * C, qkv.data_ptr() + 2 * C, 3 * C, qkv.data_ptr() + 4 * C, 3 * C, B, N, N, N, C, keep=(qkv,))
+            O1, att1_b = self._wide_self_attention(qkv, B, N, C, wide == "train") if wide else (None, None)
+            if O1 is None:
+                O1, att1_b = self._mha(qkv.data_ptr(), 3 * C, qkv.data_ptr() + 2 * C, 3 * C, qkv.data_ptr() + 4 * C, 3 * C, B, N, N, N, C,
+                                       keep=(qkv,))
         x1_t, o1_b = self._linear(O1, rows, t + ".attn1.to_out.0", C, C, resid=X0.t)
         X1 = Act(x1_t, B, x.H, x.W, C)
         # ---- cross-attention: keys / values from the context
@@ -424,7 +461,8 @@ class UNetModel(_TapeNet):
         train_fused = bool(self.fused_cross_attention_train)
         tkw = lambda n: dict(kv=None if kvs is None else kvs[n],
                              fused=(bool(self.fused_cross_attention) and fwd_only) or (train_fused and not need_grad),
-                             fused_train=train_fused and need_grad)
+                             fused_train=train_fused and need_grad,
+                             wide=("train" if need_grad else "fwd") if getattr(self, "fused_wide_self_attention", False) else None)
         # ---- time embedding (:817-818): emb = Linear(SiLU(Linear(timestep_embedding(t))))
         te = torch.empty(B, mc, dtype=torch.bfloat16, device=dev)
         check(L.sfron_timestep_embed(ptr(timesteps.to(torch.int64).contiguous()), B, mc, ptr(te), mc, stream_ptr()), "timestep_embed")

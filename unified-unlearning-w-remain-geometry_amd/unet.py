@@ -687,6 +687,9 @@ class Conditional_Model(_TapeNet):
         self.num_resolutions, self.num_res_blocks = len(ch_mult), num_res_blocks
         self.resolution, self.in_channels, self.n_classes = resolution, in_channels, n_classes
         self.attn_resolutions, self.dropout_p, self.cond_drop_prob = tuple(attn_resolutions), float(dropout), cond_drop_prob
+        # opt-in (DDPMSFRon(fused_attn=True)): AttnBlocks whose (tokens, width) sfron_wattn_supported takes run on the fused kernels of
+        # csrc/wattn.hip; the others (the 4x4 middle block: 16 tokens) keep the batched products + softmax
+        self.fused_attention = False
         self._plan()
         self._alloc()
         self._register_views()
@@ -827,6 +830,8 @@ class Conditional_Model(_TapeNet):
         qkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=dev)
         bgemm(hn, self._w(name + ".q.weight"), rows, 3 * C, C, lda=C, ldb=C, bias=self._p(name + ".q.bias"), c_bf16=qkv, ldc=3 * C)
         q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C
+        if self.fused_attention and _L().sfron_wattn_supported(T, C):
+            return self._attn_fused(tape, name, x, hn, gn_b, qkv)
         S = torch.empty(B * T, T, dtype=torch.float32, device=dev)
         bgemm(q, k, T, T, C, lda=3 * C, ldb=3 * C, batch=B, sa=T * 3 * C, sb=T * 3 * C, sc=T * T, c_f32=S, ldc=T)
         Pm = torch.empty(B * T, T, dtype=torch.bfloat16, device=dev)
@@ -856,6 +861,47 @@ class Conditional_Model(_TapeNet):
             bgemm(Pm, dO, T, C, T, lda=T, ldb=C, a_t=True, b_t=True, batch=B, sa=T * T, sb=T * C, sc=T * 3 * C, c_bf16=dv, ldc=3 * C)
             bgemm(dS, k, T, C, T, lda=T, ldb=3 * C, b_t=True, batch=B, sa=T * T, sb=T * 3 * C, sc=T * 3 * C, c_bf16=dq, ldc=3 * C)
             bgemm(dS, q, T, C, T, lda=T, ldb=3 * C, a_t=True, b_t=True, batch=B, sa=T * T, sb=T * 3 * C, sc=T * 3 * C, c_bf16=dk, ldc=3 * C)
+            colsum_bf16(dqkv, rows, 3 * C, 3 * C, self._g(name + ".q.bias"), self._cs)
+            bgemm(dqkv, hn, 3 * C, C, rows, lda=3 * C, ldb=C, a_t=True, b_t=True, c_f32=self._g(name + ".q.weight"), ldc=C)
+            d_hn = torch.empty(rows, C, dtype=torch.float32, device=dev)
+            bgemm(dqkv, self._w(name + ".q.weight"), rows, C, 3 * C, lda=3 * C, ldb=C, b_t=True, c_f32=d_hn, ldc=C)
+            gn_b(d_hn, d_out, C)                          # x.grad (+)= d_out (residual) + the norm's gradient
+        tape.append(bwd)
+        return out
+
+    def _attn_fused(self, tape, name, x, hn, gn_b, qkv):
+        """The AttnBlock from the q / k / v product on, with softmax(q k^T C^-0.5) v on the fused kernels of csrc/wattn.hip (one head of
+        width C): the tape holds qkv, O and the row statistic lse [B*T] fp32 -- no scores, no probabilities.  Everything around the
+        attention itself (proj_out, bias column sums, weight gradients, the norm) is _attn's."""
+        dev, B, C, T = self.device_, x.B, x.C, x.H * x.W
+        rows = x.rows
+        scale = float(int(C) ** (-0.5))
+        q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C
+        O = torch.empty(rows, C, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B * T, dtype=torch.float32, device=dev)
+        count_flops(4.0 * T * T * C * B)
+        check(_L().sfron_wattn_fwd(q, 3 * C, k, 3 * C, v, 3 * C, ptr(O), C, ptr(lse), B, T, 1, C, scale, stream_ptr()), "wattn_fwd")
+        out_t = torch.empty(rows, C, dtype=torch.float32, device=dev)
+        bgemm(O, self._w(name + ".proj_out.weight"), rows, C, C, lda=C, ldb=C, bias=self._p(name + ".proj_out.bias"), c_f32=out_t, ldc=C,
+              resid=x.t)
+        out = Act(out_t, B, x.H, x.W, C)
+
+        def bwd():
+            q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C     # (the closure keeps qkv alive)
+            d_out = out.grad
+            d_bf = cast_rows(d_out, C, rows, C, dev)
+            colsum_f32(d_out, rows, C, C, self._g(name + ".proj_out.bias"), self._cs)
+            bgemm(d_bf, O, C, C, rows, lda=C, ldb=C, a_t=True, b_t=True, c_f32=self._g(name + ".proj_out.weight"), ldc=C)
+            dO = torch.empty(rows, C, dtype=torch.bfloat16, device=dev)
+            bgemm(d_bf, self._w(name + ".proj_out.weight"), rows, C, C, lda=C, ldb=C, b_t=True, c_bf16=dO, ldc=C)
+            dqkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=dev)
+            dq, dk, dv = dqkv.data_ptr(), dqkv.data_ptr() + 2 * C, dqkv.data_ptr() + 4 * C
+            # the workspace (delta) comes from torch's allocator on the current stream: a graph capture takes it from the capture's pool
+            nb = _L().sfron_wattn_bwd_ws_bytes(B, T, 1, C)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            count_flops(8.0 * T * T * C * B)              # dP, dQ, dK, dV (the recomputed S is not algorithmic work)
+            check(_L().sfron_wattn_bwd(q, 3 * C, k, 3 * C, v, 3 * C, ptr(O), C, ptr(dO), C, ptr(lse), dq, 3 * C, dk, 3 * C, dv, 3 * C, B, T, 1, C,
+                                       scale, ptr(ws), nb, stream_ptr()), "wattn_bwd")
             colsum_bf16(dqkv, rows, 3 * C, 3 * C, self._g(name + ".q.bias"), self._cs)
             bgemm(dqkv, hn, 3 * C, C, rows, lda=3 * C, ldb=C, a_t=True, b_t=True, c_f32=self._g(name + ".q.weight"), ldc=C)
             d_hn = torch.empty(rows, C, dtype=torch.float32, device=dev)
