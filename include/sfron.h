@@ -922,6 +922,24 @@ int sfron_wattn_bwd(const uint16_t* q, int ldq, const uint16_t* k, int ldk, cons
                     int T, int H, int hd, float scale, void* ws, int64_t ws_bytes, void* stream);
 /* y fp32 [rows][D] = LayerNorm(x; eps) * gamma + beta (the final LayerNorm: last_hidden_state is fp32) */
 int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, float* y, void* stream);
+/* Pillow's antialiased Image.resize of one 8-bit RGB image with a crop window folded in (csrc/resample.hip), bit for bit:
+ * src uint8 [Hs][Ws][3] -> dst uint8 [Ho][Wo][3], the window of the resized image.  The filter lives in host-made tables
+ * (sfron.resample.resample_tables: Pillow's 8-bit path, PRECISION_BITS 22): kx int32 [Wo][ksx] / bx int32 [Wo][2] = (xmin, count) for the
+ * window's columns, ky [Ho][ksy] / by [Ho][2] for its rows (tables already sliced to the window by the caller; all four in device memory).
+ * Per pass, pixel and channel: ss = 2^21 + sum_{x < count} in[xmin + x] * k[x] in int32, out = clamp(ss >> 22, 0, 255) (arithmetic
+ * shift).  The horizontal pass runs first, over the window's columns and only the source rows the window's rows read, and writes uint8
+ * (that rounding is part of the result) into tmp, uint8 [rows y0..y1)[Wo][3] with [y0, y1) the union of by; the vertical pass reads tmp.
+ * An axis that keeps its size is a table of one tap of exactly 2^22.  Two launches on `stream`, no allocation, no synchronisation
+ * (graph-capturable); offsets are 64-bit; src rows need no alignment (3 * Ws bytes each).
+ * Who checks what.  This entry point sees the scalars and the addresses, not the tables' contents: SFRON_ERR_ARG, before any launch and
+ * with tmp / dst untouched, for a null pointer, a non-positive extent, ksx or ksy < 1, a row of 2 GiB or more, or tmp_bytes below one row
+ * (Wo * 3).  The tables are the caller's host data before they are uploaded, so the checks that need their contents belong to the
+ * wrapper (sfron.resample.image_resample_u8, same status code, before the upload): every bound inside the source (0 <= xmin,
+ * count >= 0, xmin + count <= Ws, count <= ksx; rows likewise against Hs), ascending row bounds, and tmp_bytes >= (y1 - y0) * Wo * 3.
+ * Behind that, the kernels clamp each bound they read into [0, Ws] / [0, Hs] / the taps per output / the rows tmp_bytes holds, so a
+ * table that slipped past gives wrong pixels, never an access outside src, tmp or dst. */
+int sfron_image_resample_u8(const uint8_t* src, int Hs, int Ws, const int32_t* kx, const int32_t* bx, int ksx, const int32_t* ky,
+                            const int32_t* by, int ksy, int Wo, int Ho, uint8_t* tmp, int64_t tmp_bytes, uint8_t* dst, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,11 @@
     python tools/bench_sd.py [--steps 5] [--batch 2] [--method full|xattn]
     python tools/bench_sd.py --fused-xattn [--batch 8] [--steps 5]     both train methods, SDSFRon(fused_xattn=False) and (fused_xattn=True) taking turns
                                                                       in one process, five rounds: minimum and spread of each
-    python tools/bench_sd.py --fused-wide-attn [--batch 8]             the same A-B of SDSFRon(fused_wide_attn=...) (csrc/wattn.hip)"""
+    python tools/bench_sd.py --fused-wide-attn [--batch 8]             the same A-B of SDSFRon(fused_wide_attn=...) (csrc/wattn.hip)
+    python tools/bench_sd.py --from-images [--batch 8] [--steps 5]     the driver loop sd.nsfw_removal from image folders: synthetic 768x1024
+                                                                      photographs written with Pillow into a temporary folder, the KL-f8
+                                                                      encoder with random weights, host resize and GPU resize in turn, and
+                                                                      the same loop fed with resident latents"""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +17,7 @@ ap.add_argument("--method", default="full")
 ap.add_argument("--eager", action="store_true", help="no HIP-graph replay of the stages")
 ap.add_argument("--fused-xattn", action="store_true", help="A-B of the fused differentiable cross-attention (flag off = the default path)")
 ap.add_argument("--fused-wide-attn", action="store_true", help="A-B of the fused wide-head self-attention (flag off = the default path)")
+ap.add_argument("--from-images", action="store_true", help="time sd.nsfw_removal over image folders (front end included)")
 a = ap.parse_args()
 AB = ("fused_xattn", "fused_cross_attention_train") if a.fused_xattn else ("fused_wide_attn", "fused_wide_self_attention") if a.fused_wide_attn else None
 from sfron import sd, sd_unet
@@ -40,6 +45,52 @@ def batch():
     return (dict(x_f=xf, x_p=xf, c_f=c_f, c_p=c_p, t=torch.randint(0, 1000, (B,), device=DEV, generator=gd), noise=rn(B, 4, 64, 64)),
             dict(x=rn(B, 4, 64, 64), c=c_p, t=torch.randint(0, 1000, (B,), device=DEV, generator=gd), noise=rn(B, 4, 64, 64)))
 bts = [batch() for _ in range(2)]
+if a.from_images:
+    # the driver loop with the front end in it.  Prompt contexts are encoded once before the loop, so a stand-in cond stage (fixed random
+    # [n, 77, 768]) leaves the timed part unchanged; the VAE encoder runs at its real size on random weights.
+    import tempfile
+    import numpy as np
+    from PIL import Image
+    from sfron import vae
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_resample import photograph
+    enc = vae.VAEEncoder()
+    gw = torch.Generator().manual_seed(3)
+    enc.load_state_dict({("encoder." + n if not n.startswith("quant_conv.") else n): (torch.randn(shp, generator=gw) * (0.02 if len(shp) > 1 else 0.1)
+                                                                                     + (1.0 if "norm" in n and n.endswith("weight") else 0.0))
+                         for n, shp in enc.specs.items()})
+
+    class _Cond:
+        def encode(self, prompts):
+            return rn(1, 77, 768).expand(len(prompts), -1, -1).contiguous()
+
+    ldm = sd.LatentDiffusion(model, cond_stage_model=_Cond(), first_stage_encoder=enc)
+    warm = 3
+    with tempfile.TemporaryDirectory() as d:
+        for name in ("forget", "remain"):
+            os.makedirs(os.path.join(d, name))
+            for i in range(2 * B):
+                photograph(768, 1024, i + (100 if name == "remain" else 0)).save(os.path.join(d, name, f"{i:03d}.jpg"), quality=92)
+        res = {}
+        for gpu_resize in (False, True, False, True):
+            fl = sd.ConceptImageLoader(os.path.join(d, "forget"), B, gpu_resize=gpu_resize)
+            rl = sd.ConceptImageLoader(os.path.join(d, "remain"), B, gpu_resize=gpu_resize)
+            marks = {}
+
+            def mark(runner, step):
+                if step in (warm, warm + a.steps):
+                    torch.cuda.synchronize(); marks[step] = time.time()
+            sd.nsfw_removal(ldm, fl, rl, warm + a.steps, a.method, use_graphs=not a.eager, log_every=0, save_every=1, on_save=mark)
+            res.setdefault(gpu_resize, []).append((marks[warm + a.steps] - marks[warm]) / a.steps * 1e3)
+    run = sd.SDSFRon(model, lr=1e-5, train_method=a.method, use_graphs=not a.eager)
+    for i in range(warm): run.step(*bts[i % 2])
+    torch.cuda.synchronize(); t0 = time.time()
+    for i in range(a.steps): run.step(*bts[i % 2])
+    torch.cuda.synchronize(); lat = (time.time() - t0) / a.steps * 1e3
+    print(f"SD v1 nsfw_removal from image folders (768x1024 JPEG -> 512 px), batch {B}, train_method {a.method}, "
+          f"{'eager' if a.eager else 'graph replay'}, ms per iteration over {a.steps} (two runs each): host resize {res[False][0]:.1f} / {res[False][1]:.1f}, "
+          f"GPU resize {res[True][0]:.1f} / {res[True][1]:.1f}; resident latents (SDSFRon.step alone) {lat:.1f}")
+    sys.exit(0)
 if AB:
     # one model, one runner per mode (each with its own graphs); the switch is read when a stage is run eagerly or captured
     for method in ("full", "xattn"):

@@ -311,7 +311,9 @@ _PROTOS.update({
     "sfron_wattn_bwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int,
                                 c_int, c_float, _P, c_int64, _S]),
 })
-ERR_UNSUPPORTED = 1002          # SFRON_ERR_UNSUPPORTED (csrc/common.h)
+_PROTOS["sfron_image_resample_u8"] = (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, _S])
+ERR_ARG = 1001                  # SFRON_ERR_ARG
+ERR_UNSUPPORTED = 1002         # SFRON_ERR_UNSUPPORTED (csrc/common.h)
 
 
 class WprepItem(ctypes.Structure):        # sfron_wprep_item

@@ -187,3 +187,36 @@ class SDFisherAccumulator:
     def state_dict(self):
         """name -> fp32 CPU tensor keyed by the UNet-relative parameter names (generate_fisher.py:31-32,79: nude_forget.pt / nude_remain.pt)."""
         return {n: self.unet.view(self.fisher, n).detach().cpu().clone() for n in self.unet.index}
+
+
+def sd_generate_fisher(model, forget_loader, remain_loader, c_guidance=7.5, forget_prompt="a photo of a nude person",
+                       remain_prompt="a photo of a person wearing clothes", seed=0):
+    """The two loops of SD/train-scripts/generate_fisher.py (:36-79 forget, :87-128 remain) over ``SDFisherAccumulator``, from images and
+    prompts: ``model`` a sd.LatentDiffusion with the VAE encoder and the text encoder attached, the loaders sd.ConceptImageLoader-s.  One
+    pass over each loader from its first batch, n_batches = len(loader).  Per batch the images are encoded once (the reference's second
+    get_input, for the null prompt, only re-draws a latent it never reads), the prompt and "" are encoded once before the loop as
+    [1, 77, D] and expanded to the batch's rows, and the draws come from one device generator seeded with ``seed`` in the order
+    eps, t, noise, the forget loop first.  The model is put in eval mode (:25) and left there.  Returns the two state dicts
+    (forget, remain) that ``mask_from_fisher`` / sd masks take, keyed by the UNet-relative parameter names."""
+    enc, unet = model.first_stage_encoder, model.model.diffusion_model
+    if enc is None or model.cond_stage_model is None:
+        raise NotImplementedError("sd_generate_fisher needs a LatentDiffusion with first_stage_encoder and cond_stage_model attached")
+    model.eval()
+    dev, T = model.device, model.num_timesteps
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    c_null = model.get_learned_conditioning([""])
+    out = []
+    for loader, prompt in ((forget_loader, forget_prompt), (remain_loader, remain_prompt)):
+        c = model.get_learned_conditioning([prompt])
+        if hasattr(loader, "reset"):
+            loader.reset()
+        acc = SDFisherAccumulator(unet, model.schedule, len(loader), c_guidance=c_guidance)
+        for _ in range(len(loader)):
+            post = model.encode_first_stage(loader.next())
+            n, z2, h, w = post.parameters.shape
+            x = post.sample(eps=torch.randn(n, z2 // 2, h, w, generator=gen, device=dev), scale=model.scale_factor)
+            t = torch.randint(0, T, (n,), generator=gen, device=dev).long()
+            noise = torch.randn(n, z2 // 2, h, w, generator=gen, device=dev)
+            acc.accumulate(dict(x=x, c=c.expand(n, -1, -1).contiguous(), c_null=c_null.expand(n, -1, -1).contiguous(), t=t, noise=noise))
+        out.append(acc.state_dict())
+    return out[0], out[1]
