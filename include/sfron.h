@@ -941,6 +941,31 @@ int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* bet
 int sfron_image_resample_u8(const uint8_t* src, int Hs, int Ws, const int32_t* kx, const int32_t* bx, int ksx, const int32_t* ky,
                             const int32_t* by, int ksy, int Wo, int Ho, uint8_t* tmp, int64_t tmp_bytes, uint8_t* dst, void* stream);
 
+/* ------------------------------------------------------------------ DDPM guided sampling (ddpm_sample.hip)
+ * Classifier-free guidance + one generalized step of DDPM/functions/denoising.py:72-95 in one pass:
+ *   e = (1 + cond_scale) * eps_cond + (-cond_scale) * eps_null   (eps_null NULL: e = eps_cond, the reference's cond_scale == 0 case, or a
+ *                                                                 model that hands over the combined epsilon)
+ *   x0_pred = (x - e*s1)/s2;  x_next = (s3*x0_pred + c1*noise) + c2*e
+ * with (s1, s2, s3, c1, c2) = coef[k], k = *step clamped into [0, steps): coef is a DEVICE table float [steps][5] in the meaning of
+ * sfron_ddim_step, step a DEVICE int32, so a captured graph replays unchanged for every step.  Bit-equal to sfron_axpby(eps_cond,
+ * eps_null, 1.0 + cond_scale, -cond_scale) followed by sfron_ddim_step with that row, for every scale: cond_scale is a double, and
+ * 1.0 + cond_scale and -cond_scale are each rounded once to fp32, as a caller's double expressions are on their way into sfron_axpby.  noise may be NULL where every c1 is 0 (a NULL
+ * noise counts as zeros), x0_pred may be NULL, x_next may be x; 64-bit element count.  The table's contents are the caller's: a row with
+ * s2 == 0 is refused where the table is built on the host (sfron.ddpm.generalized_coefficients).  SFRON_ERR_ARG before any launch for a
+ * null pointer, n or steps < 1, a cond_scale that is not finite, or an x0_pred that aliases x or x_next. */
+int sfron_ddpm_guided_step(const float* x, const float* eps_cond, const float* eps_null, const float* noise, double cond_scale,
+                           const float* coef, int steps, const int32_t* step, int64_t n, float* x_next, float* x0_pred, void* stream);
+/* The step counter of a sampling loop, one workgroup: k = *step clamped into [0, steps); t[0 .. nt) = tseq[min(k + 1, steps - 1)] (the
+ * model's float timestep input for the next step, tseq a device table float [steps]); *step = k + 1.  A launch of its own behind the
+ * step kernel: a step kernel that incremented the index itself would race with its own workgroups that have not read it yet. */
+int sfron_ddpm_sampler_advance(const float* tseq, int steps, int32_t* step, float* t, int nt, void* stream);
+/* The bytes of torchvision save_image(x[k], path, normalize=True) for every image of a batch in one launch: x fp32 [B][3][H][W] -> out
+ * uint8 [B][H][W][3], each image scaled by its OWN minimum lo and maximum hi, hi = max(hi, lo + 1e-5), then exactly the byte arithmetic
+ * of sfron_rows_to_image_u8 in SFRON_IMAGE_SAVE_IMAGE mode.  One workgroup per image; B*H*W*3 < 2^31 (else SFRON_ERR_ARG, nothing
+ * launched).  An image for which hi > lo does not hold after that rule (a constant image with |lo| >= 128, or no finite value), which
+ * sfron_rows_to_image_u8 would refuse, gets bytes of 0. */
+int sfron_images_normalize_u8(const float* x, int B, int H, int W, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

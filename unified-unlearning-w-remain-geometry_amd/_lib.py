@@ -312,6 +312,11 @@ _PROTOS.update({
                                 c_int, c_float, _P, c_int64, _S]),
 })
 _PROTOS["sfron_image_resample_u8"] = (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, _S])
+_PROTOS.update({
+    "sfron_ddpm_guided_step": (c_int, [_P, _P, _P, _P, c_double, _P, c_int, _P, c_int64, _P, _P, _S]),
+    "sfron_ddpm_sampler_advance": (c_int, [_P, c_int, _P, _P, c_int, _S]),
+    "sfron_images_normalize_u8": (c_int, [_P, c_int, c_int, c_int, _P, _S]),
+})
 ERR_ARG = 1001                  # SFRON_ERR_ARG
 ERR_UNSUPPORTED = 1002         # SFRON_ERR_UNSUPPORTED (csrc/common.h)
 

@@ -129,35 +129,192 @@ def compute_alpha(beta, t):
     return alphas_cumprod(beta).index_select(0, t + 1)
 
 
+def generalized_row(abar, i, j, eta):
+    """(s1, s2, s3, c1, c2) of one generalized step from timestep i to j (j = -1: the last step) in the meaning of sfron_ddim_step:
+    DDPM/functions/denoising.py:85-92 in torch's fp32 0-dim tensor math.  ``abar``: CPU fp32 [T + 1], alpha_bar of timestep t at index
+    t + 1 and alpha_bar(-1) = 1 at index 0.  A step whose s2 = sqrt(alpha_bar_i) is 0 would divide by zero on the device: refused here."""
+    at, at_next = abar[i + 1], abar[j + 1]                                                 # fp32 0-dim tensors: torch's scalar math
+    c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
+    c2 = ((1 - at_next) - c1 ** 2).sqrt()
+    row = (float((1 - at).sqrt()), float(at.sqrt()), float(at_next.sqrt()), float(c1), float(c2))
+    if row[1] == 0.0:
+        raise _lib.SfronError(f"generalized step {i} -> {j}: sqrt(alpha_bar) is 0, the update would divide by it")
+    return row
+
+
+def generalized_coefficients(abar, seq, eta=0.0):
+    """The coefficient table of a whole sampling run, in execution order (``seq`` reversed): a list of (s1, s2, s3, c1, c2) rows and the
+    list of timesteps the model sees.  The ONE host helper behind generalized_steps_conditional and DDPMSampler."""
+    seq = [int(s) for s in seq]
+    seq_next = [-1] + seq[:-1]
+    eta = float(eta)
+    steps = list(zip(reversed(seq), reversed(seq_next)))
+    return [generalized_row(abar, i, j, eta) for i, j in steps], [i for i, _ in steps]
+
+
+def _abar_host(b):
+    return torch.cat([torch.ones(1, device=b.device), alphas_cumprod(b)]).cpu()           # index t+1; alpha_bar(-1) = 1
+
+
 def generalized_steps_conditional(x, c, seq, model, b, cond_scale=3.0, step_noise=None, **kwargs):
     """DDPM/functions/denoising.py:72-95: the classifier-free-guided generalized (DDIM, ``eta``) sampler the runner's snapshot
     path uses.  Returns (xs, x0_preds) like the reference (tensors stay on the device).  The denoiser is the caller's
     ``model(x, t, c, cond_scale=..., mode="test")``; the update runs in sfron_ddim_step.  ``step_noise[k]`` optionally fixes
-    the k-th ``randn_like`` draw."""
+    the k-th ``randn_like`` draw.  The coefficients of all steps are formed before the first one (generalized_coefficients: the same fp32
+    values as step by step); one difference from the earlier form: a step whose sqrt(alpha_bar) is 0 -- no schedule of the reference
+    has one -- now raises SfronError before anything runs instead of being refused by sfron_ddim_step when the loop reaches it."""
     eta = float(kwargs.get("eta", 0))
-    abar = torch.cat([torch.ones(1, device=b.device), alphas_cumprod(b)]).cpu()          # index t+1; alpha_bar(-1) = 1
+    rows, ts = generalized_coefficients(_abar_host(b), seq, eta)
     with torch.no_grad():
         n = x.size(0)
-        seq = list(seq)
-        seq_next = [-1] + seq[:-1]
         xs, x0_preds = [x], []
-        for k, (i, j) in enumerate(zip(reversed(seq), reversed(seq_next))):
+        for k, (i, (s1, s2, s3, c1, c2)) in enumerate(zip(ts, rows)):
             t = (torch.ones(n) * i).to(x.device)
-            at, at_next = abar[i + 1], abar[j + 1]                                         # fp32 0-dim tensors: torch's scalar math
             et = model(xs[-1], t, c, cond_scale=cond_scale, mode="test").contiguous().float()
-            c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
-            c2 = ((1 - at_next) - c1 ** 2).sqrt()
             noise = None
             if eta != 0.0:
                 noise = (torch.randn_like(x) if step_noise is None else step_noise[k]).contiguous()
             xt = xs[-1].contiguous().float()
             x_next, x0 = torch.empty_like(xt), torch.empty_like(xt)
-            check(_lib.lib().sfron_ddim_step(ptr(xt), ptr(et), ptr(noise), xt.numel(), float((1 - at).sqrt()), float(at.sqrt()),
-                                             float(at_next.sqrt()), float(c1), float(c2), ptr(x_next), ptr(x0), stream_ptr()),
+            check(_lib.lib().sfron_ddim_step(ptr(xt), ptr(et), ptr(noise), xt.numel(), s1, s2, s3, c1, c2, ptr(x_next), ptr(x0), stream_ptr()),
                   "ddim_step")
             x0_preds.append(x0)
             xs.append(x_next)
     return xs, x0_preds
+
+
+def sampling_sequence(skip_type="uniform", num_timesteps=1000, timesteps=1000):
+    """The timestep sequence of Diffusion.sample_image (DDPM/runners/diffusion.py:831-842), ascending.  "uniform":
+    range(0, T, T // timesteps) -- MORE than ``timesteps`` entries where T % timesteps != 0, as the reference has it; "quad":
+    int(linspace(0, sqrt(0.8 T), timesteps)[k] ** 2)."""
+    if skip_type == "uniform":
+        return list(range(0, num_timesteps, num_timesteps // timesteps))
+    if skip_type == "quad":
+        return [int(s) for s in list(np.linspace(0, np.sqrt(num_timesteps * 0.8), timesteps) ** 2)]
+    raise NotImplementedError(f"skip_type {skip_type!r} (DDPM/runners/diffusion.py:831-844 defines 'uniform' and 'quad')")
+
+
+class DDPMSampler:
+    """Diffusion.sample_image (DDPM/runners/diffusion.py:825-872) for sample_type "generalized": classifier-free-guided DDIM-style
+    sampling whose step is ONE guided forward pass and ONE fused update launch (sfron_ddpm_guided_step), with the step's coefficients
+    and timestep read on the device through a step index that sfron_ddpm_sampler_advance moves -- so one captured step replays for the
+    whole run (``graph=True``).
+
+    model: ``sfron.unet.Conditional_Model`` (anything with ``forward_pair``) takes the batch-2B route -- both guidance branches in one
+    pass, dropout off whatever the model's mode; ``cond_scale == 0`` runs the conditional branch alone at batch B.  Any other callable is
+    called as ``model(x, t, c, cond_scale=..., mode="test")`` and its combined epsilon goes through the same kernel.  Negative scales are
+    legal (sample.py itself uses -1).
+    eta != 0: each step's noise is drawn from ``generator`` (on its device; None: the default generator of the images' device) into one
+    static buffer, in step order.
+    graph: capture one step (pair forward, guided step, advance) after an eager first step and replay it; at most ONE graph per sampler,
+    for the first (batch shape, cond_scale) it sees -- any other batch (the short last round) runs eagerly.  ``last=False`` runs eagerly
+    too (it keeps every step's tensors).  Default False.
+    sample_type "ddpm_noisy" is not available: the reference imports a name that does not exist there."""
+
+    def __init__(self, model, betas, sample_type="generalized", skip_type="uniform", timesteps=1000, eta=0.0, graph=False, generator=None):
+        if sample_type == "ddpm_noisy":
+            raise NotImplementedError("sample_type 'ddpm_noisy': DDPM/runners/diffusion.py:865 imports ddpm_steps_conditional, which "
+                                      "functions/denoising.py does not define (SURVEY.md section 9 Q16)")
+        if sample_type != "generalized":
+            raise NotImplementedError(f"sample_type {sample_type!r}")
+        self.model, self.eta, self.graph, self.generator = model, float(eta), bool(graph), generator
+        self.seq = sampling_sequence(skip_type, int(betas.numel()), int(timesteps))
+        rows, ts = generalized_coefficients(_abar_host(betas), self.seq, self.eta)
+        dev = betas.device
+        self.steps = len(rows)
+        self.coef = torch.tensor(rows, dtype=torch.float32, device=dev).contiguous()            # [steps][5]
+        self.tseq = torch.tensor(ts, dtype=torch.float32, device=dev)
+        self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._pair = hasattr(model, "forward_pair")
+        self._g = None                    # the one captured step: dict(key, graph, x, t, c, noise)
+
+    # one step on the buffers it is given: model pass, guided update, advance.  Stream-ordered device work only.
+    def _step(self, x, t, c, noise, cond_scale, x_next, x0_pred):
+        L = _lib.lib()
+        if self._pair:
+            ec, en = self.model.forward_pair(x, t, c, with_null=cond_scale != 0)
+        else:
+            ec, en = self.model(x, t, c, cond_scale=cond_scale, mode="test").contiguous().float(), None
+        check(L.sfron_ddpm_guided_step(ptr(x), ptr(ec), ptr(en), ptr(noise), float(cond_scale), ptr(self.coef), self.steps, ptr(self.step_idx),
+                                       x.numel(), ptr(x_next), ptr(x0_pred), stream_ptr()), "ddpm_guided_step")
+        check(L.sfron_ddpm_sampler_advance(ptr(self.tseq), self.steps, ptr(self.step_idx), ptr(t), t.numel(), stream_ptr()), "ddpm_sampler_advance")
+
+    def _draw(self, noise):
+        g = self.generator
+        if g is not None and g.device != noise.device:
+            noise.copy_(torch.randn(noise.shape, generator=g, device=g.device))
+        else:
+            noise.normal_(generator=g)
+
+    def _capture(self, st, cond_scale):
+        import gc
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        # graphs.StageGraph's capture discipline: no cyclic collection while the stream captures, a private memory pool
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, pool=torch.cuda.graph_pool_handle()):
+                self._step(st["x"], st["t"], st["c"], st["noise"], cond_scale, st["x"], None)
+        finally:
+            if gc_was_on:
+                gc.enable()
+        st["graph"] = graph
+
+    @torch.no_grad()
+    def sample_image(self, x, c, cond_scale, last=True):
+        """x: the starting noise [B, C, H, W]; c: int64 labels [B].  last=True: the final image batch; last=False: (xs, x0_preds), the lists
+        generalized_steps_conditional returns (xs[0] is ``x``)."""
+        cond_scale = float(cond_scale)
+        x = x.float().contiguous()
+        c = c.contiguous()
+        B = x.shape[0]
+        m = self.model
+        prep = hasattr(m, "_prep_conv_weights")
+        if prep:
+            # the weights do not change while a run samples: re-lay the convolution operands once (if the model asks for it) instead of
+            # in every pass, and hand the model back as it was -- its "operands are stale" flag included: a training loop that captures
+            # its next stage into a graph decides by that flag whether the graph re-lays them
+            was_auto, was_dirty = m.auto_prep, getattr(m, "_conv_dirty", True)
+            m._prep_conv_weights()
+            m.auto_prep = False
+        try:
+            key = (tuple(x.shape), c.dtype, cond_scale)
+            use_graph = self.graph and last and (self._g is None or self._g["key"] == key)
+            self.step_idx.zero_()
+            if use_graph and self._g is not None:
+                st = self._g
+                st["x"].copy_(x)
+                st["c"].copy_(c)
+                st["t"].fill_(float(self.seq[-1]))
+            else:
+                st = dict(key=key, graph=None, x=x.clone(), c=c.clone(), t=torch.full((B,), float(self.seq[-1]), dtype=torch.float32, device=x.device),
+                          noise=torch.empty_like(x) if self.eta != 0.0 else None)
+            if not last:
+                xs, x0s = [x], []
+                for _ in range(self.steps):
+                    if st["noise"] is not None:
+                        self._draw(st["noise"])
+                    x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+                    self._step(xs[-1], st["t"], st["c"], st["noise"], cond_scale, x_next, x0)
+                    xs.append(x_next)
+                    x0s.append(x0)
+                return xs, x0s
+            for k in range(self.steps):
+                if st["noise"] is not None:
+                    self._draw(st["noise"])
+                if use_graph and st["graph"] is not None:
+                    st["graph"].replay()
+                    continue
+                self._step(st["x"], st["t"], st["c"], st["noise"], cond_scale, st["x"], None)
+                if use_graph and k == 0 and self.steps > 1:          # the eager first step was the warm-up
+                    self._capture(st, cond_scale)
+                    self._g = st
+            return st["x"].clone() if st is self._g else st["x"]
+        finally:
+            if prep:
+                m.auto_prep, m._conv_dirty = was_auto, was_dirty
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -339,6 +496,13 @@ class DDPMSFRon:
         self.opt.g2 = None
         self._weights_updated()
         return {"forget_loss": ori_forget, "remain_loss": ori_remain, "alpha": alpha}
+
+    def sampler(self, **kwargs):
+        """A DDPMSampler over the LIVE model and this runner's schedule (keywords: DDPMSampler's).  Sampling between two ``step`` calls
+        leaves the next step as it would have been, with ``use_graphs`` or without: no dropout draw, no change of mode, and the model's
+        record of whether its convolution operands are stale is handed back as found (the next stage, eager or being captured, re-lays
+        them exactly where it would have)."""
+        return DDPMSampler(self.model, self.b, **kwargs)
 
     def ema_state_dict(self):
         return {n: v.clone() for n, v in self.flat.named_views(self.shadow).items()}

@@ -16,6 +16,7 @@ and one dropout mask per ResnetBlock (:131) -- are drawn here on the device, or 
 so that a test can give the oracle the very same draws.
 """
 import ctypes
+import itertools
 from collections import OrderedDict
 from types import SimpleNamespace
 
@@ -1146,6 +1147,23 @@ class Conditional_Model(_TapeNet):
         out = torch.empty_like(logits)
         check(_L().sfron_axpby(ptr(logits), ptr(null), 1.0 + cond_scale, -float(cond_scale), logits.numel(), ptr(out), stream_ptr()), "axpby")
         return out
+
+    @torch.no_grad()
+    def forward_pair(self, x, t, c, with_null=True):
+        """Both guidance branches of ``mode="test"`` (models/diffusion.py:340-357) in ONE pass at batch 2B: [x; x], [t; t], [c; c] with the
+        keep mask [1 .. 1, 0 .. 0].  Returns (conditional, null), two views of one [2B, ...] tensor; the caller mixes them
+        (sfron_ddpm_guided_step).  ``with_null=False`` (the reference's cond_scale == 0 case) runs the conditional branch alone at batch B
+        and returns (conditional, None).  No gradients, and no dropout whatever ``self.training`` says: the pass hands ``_run`` an
+        explicit all-None mask list, so neither the mode nor the dropout counter / plans are touched."""
+        B, dev = x.shape[0], self.device_
+        x = x.float()
+        keep = torch.zeros(2 * B if with_null else B, dtype=torch.uint8, device=dev)        # two fills per pass: capturable, nothing to keep
+        keep[:B] = 1
+        if not with_null:
+            out, _ = self._run(x, t, c, keep, itertools.repeat(None), need_grad=False)
+            return out, None
+        out, _ = self._run(torch.cat([x, x]), torch.cat([t, t]), torch.cat([c, c]), keep, itertools.repeat(None), need_grad=False)
+        return out[:B], out[B:]
 
 
 class _UNetFn(torch.autograd.Function):
