@@ -421,7 +421,8 @@ typedef struct sfron_conv_desc {
                                        *split_pending (> 0) slabs [rows * n_out] in split_ws and does NOT launch the pass that adds them and
                                        applies bias / sample_vec / resid -- the caller hands them to a GroupNorm that finishes the sum itself
                                        (sfron_split_src, sfron_groupnorm_*_src) or to sfron_split_finish; 0 = the output is complete.
-                                       NULL = always complete. */
+                                       NULL = always complete.  Needs out_f32: with out_bf16 set the call is refused (SFRON_ERR_ARG)
+                                       before any launch, *split_pending = 0 and neither the output nor split_ws is written. */
 } sfron_conv_desc;
 /* out[p][n] = sum_{tap, c} src[src(p, tap)][c] * w[n][tap][c]; w bf16 [n_out][taps][c_src] (sfron_conv_wprep's "fwd" layout;
  * the input gradient calls this on dY with the "dgrad" layout) */

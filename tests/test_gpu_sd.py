@@ -162,7 +162,8 @@ def test_sd_v1_unet_forward_backward_vs_oracle_at_full_size():
     _compare_unet(ref, model, x, t, ctx, w, "SD v1 UNet (859.5 M parameters) B=1 64x64 ctx 77x768")
 
 
-@pytest.mark.parametrize("cfg,B,S,Lc", [(SMALL, 3, 8, 5), (MID, 2, 32, 77), (HD160, 2, 8, 77)])
+# (S = 12 and 24: latents of 96 / 192 px images, levels 12 / 6 and 24 / 12 / 6 -- no side a power of two)
+@pytest.mark.parametrize("cfg,B,S,Lc", [(SMALL, 3, 8, 5), (MID, 2, 32, 77), (HD160, 2, 8, 77), (SMALL, 3, 12, 5), (MID, 1, 24, 77)])
 def test_sd_unet_forward_backward_vs_oracle(cfg, B, S, Lc):
     ref, model = _pair(cfg, seed=B)
     ref.train(); model.train()
@@ -172,6 +173,36 @@ def test_sd_unet_forward_backward_vs_oracle(cfg, B, S, Lc):
     ctx = torch.randn(B, Lc, cfg["context_dim"], generator=g)
     w = torch.randn(B, 4, S, S, generator=g) * 0.1
     _compare_unet(ref, model, x, t, ctx, w, f"SD UNet mc={cfg['model_channels']} B={B} {S}x{S} ctx {Lc}")
+
+
+def test_self_attention_at_36_tokens_pads_its_keys():
+    """A 6 x 6 level (the middle block of a 384 px image) has 36 tokens, no multiple of 8: attn1 then runs _mha on per-sample zero-padded copies
+    of its keys and values (_mha_padded_self); before, the score product refused the shape.  O and all of d qkv against float64 softmax
+    attention on the same bf16 inputs, per (sample, head) in the relative 2-norm at the bound of tests/test_gpu_attention_grid.py (2e-2; the
+    roundings are the same: P, dS and the results to bf16).  A padded key with any weight, or a gradient row copied back to the wrong token,
+    is an error of order 1."""
+    from sfron import sd_unet
+    model = sd_unet.UNetModel(**SMALL)
+    B, N, C, h = 3, 36, 64, SMALL["num_heads"]
+    d = C // h
+    g = torch.Generator().manual_seed(36)
+    qkv = torch.randn(B * N, 3 * C, generator=g).to(torch.bfloat16)
+    d_o = (torch.randn(B * N, C, generator=g) * 0.2).to(torch.bfloat16)
+    O, bwd = model._mha_padded_self(qkv.to(DEV), B, N, C)
+    dqkv = torch.full((B * N, 3 * C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    bwd(d_o.to(DEV), dqkv)
+    x = qkv.double().requires_grad_(True)
+    q, k, v = x.view(B, N, 3, h, d).permute(2, 0, 3, 1, 4).unbind(0)
+    o_ref = ((q @ k.transpose(-2, -1)) * d ** -0.5).softmax(-1) @ v
+    o_ref = o_ref.transpose(1, 2).reshape(B * N, C)
+    o_ref.backward(d_o.double())
+    assert bool(torch.isfinite(dqkv.float()).all()), "d qkv was not written everywhere"
+    got = torch.cat([O.cpu().double(), dqkv.cpu().double()], dim=1).view(B, N, 4, h, d)
+    want = torch.cat([o_ref.detach(), x.grad], dim=1).view(B, N, 4, h, d)
+    err = (got - want).norm(dim=(1, 4)) / want.norm(dim=(1, 4))          # [B][O, dq, dk, dv][h]
+    print("36-token self-attention, worst relative 2-norm per (sample, head): " +
+          ", ".join(f"{nm} {float(err[:, i].max()):.3e}" for i, nm in enumerate(("O", "dq", "dk", "dv"))))
+    assert float(err.max()) < 2e-2, err
 
 
 # 2 x the worst per-tensor value measured on MI355X (round 5; printed by the test): xattn / as_written min cosine 0.9870, norm ratios within

@@ -401,7 +401,9 @@ SMALL = dict(ch=128, ch_mult=(1, 2), num_res_blocks=1, attn_resolutions=(8,), dr
 CIFAR = dict(ch=128, ch_mult=(1, 2, 2, 2), num_res_blocks=2, attn_resolutions=(16,), dropout=0.1, resolution=32, n_classes=10)
 
 
-@pytest.mark.parametrize("cfg,B,p_drop", [(SMALL, 4, 0.0), (SMALL, 3, 0.1), (CIFAR, 8, 0.1)])
+# (the 24 px case: levels 24 / 12, no side a power of two -- the (b, ho, wo) decode of the convolution tiles divides instead of shifting)
+@pytest.mark.parametrize("cfg,B,p_drop", [(SMALL, 4, 0.0), (SMALL, 3, 0.1), (CIFAR, 8, 0.1),
+                                          (dict(SMALL, resolution=24, attn_resolutions=(12,)), 3, 0.1)])
 def test_unet_forward_backward_vs_oracle(cfg, B, p_drop):
     ref, model = _pair(cfg, seed=B)
     model.dropout_p = p_drop if p_drop > 0 else 0.0

@@ -2383,6 +2383,8 @@ static int conv_geom(const sfron_conv_desc* d, ConvGeom& c, int src_c) {
 int sfron_conv_fwd(const sfron_conv_desc* d, const uint16_t* src, const uint16_t* w, void* stream) {
   SFRON_CHECK_ARG(d && src && w && d->n_out % 4 == 0);
   if (d->split_pending) *d->split_pending = 0;
+  // a pending split leaves fp32 slabs for a GroupNorm (or sfron_split_finish) to turn into the fp32 output: with out_bf16 nobody would write it
+  SFRON_CHECK_ARG(!(d->split_pending && d->out_bf16));
   BGemmArgs g{};
   int rc = conv_geom(d, g.cg, d->c_src); if (rc) return rc;
   g.A = (const __bf16*)src; g.B = (const __bf16*)w;

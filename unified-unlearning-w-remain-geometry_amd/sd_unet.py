@@ -234,6 +234,22 @@ class UNetModel(_TapeNet):
                       sb2=d, sc2=d, c_bf16=dv, ldc=ldv)
         return O, bwd
 
+    def _mha_padded_self(self, qkv, B, N, C):
+        """attn1 through _mha at a token count that is no multiple of 8 (the 6 x 6 level of a 384 px image: 36 tokens).  _mha's products need
+        the key count % 8 == 0, so the keys and values move to a buffer of their own, padded per sample to a multiple of 8 with zero rows that
+        get probability 0 -- what _pad_context does for attn2.  backward(dO bf16, dqkv bf16 [B*N][3C] tensor) fills all of dqkv."""
+        dev = self.device_
+        Np = _pad8(N)
+        kv = torch.zeros(B, Np, 2 * C, dtype=torch.bfloat16, device=dev)
+        kv[:, :N].copy_(qkv.view(B, N, 3 * C)[:, :, C:])
+        O, mha_b = self._mha(qkv.data_ptr(), 3 * C, kv.data_ptr(), 2 * C, kv.data_ptr() + 2 * C, 2 * C, B, N, Np, N, C, keep=(qkv, kv))
+
+        def bwd(dO, dqkv):
+            dkv = torch.empty(B, Np, 2 * C, dtype=torch.bfloat16, device=dev)
+            mha_b(dO, dqkv.data_ptr(), dkv.data_ptr(), dkv.data_ptr() + 2 * C)
+            dqkv.view(B, N, 3 * C)[:, :, C:].copy_(dkv[:, :N])
+        return O, bwd
+
     def _flash_self_attention(self, qkv, B, N, C):
         """Self-attention through the fused flash-style kernels of csrc/attn.hip (qkv [B*N][3C], column = which * C + head * d + i)."""
         h = self.heads
@@ -373,12 +389,15 @@ class UNetModel(_TapeNet):
         n1, ln1_b = self._layernorm(X0, t + ".norm1")
         qkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=dev)
         wqkv = self._w(t + ".attn1.to_q.weight")
+        pad1 = False                                                    # attn1 runs on padded copies of its keys / values (_mha_padded_self)
         bgemm(n1, wqkv, rows, 3 * C, C, lda=C, ldb=C, c_bf16=qkv, ldc=3 * C)
         if (C // self.heads) <= 80 and (C // self.heads) % 8 == 0 and N % 64 == 0:
             O1, att1_b = self._flash_self_attention(qkv, B, N, C)       # scores never leave the chip (4096 tokens at 64x64)
         else:
             O1, att1_b = self._wide_self_attention(qkv, B, N, C, wide == "train") if wide else (None, None)
-            if O1 is None:
+            if O1 is None and N % 8:
+                O1, att1_b, pad1 = self._mha_padded_self(qkv, B, N, C) + (True,)
+            elif O1 is None:
                 O1, att1_b = self._mha(qkv.data_ptr(), 3 * C, qkv.data_ptr() + 2 * C, 3 * C, qkv.data_ptr() + 4 * C, 3 * C, B, N, N, N, C,
                                        keep=(qkv,))
         x1_t, o1_b = self._linear(O1, rows, t + ".attn1.to_out.0", C, C, resid=X0.t)
@@ -432,7 +451,10 @@ class UNetModel(_TapeNet):
             d1 = X1.grad
             dO1b = o1_b(d1, C, dx_bf16=True)
             dqkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=dev)
-            att1_b(dO1b, dqkv.data_ptr(), dqkv.data_ptr() + 2 * C, dqkv.data_ptr() + 4 * C)
+            if pad1:
+                att1_b(dO1b, dqkv)
+            else:
+                att1_b(dO1b, dqkv.data_ptr(), dqkv.data_ptr() + 2 * C, dqkv.data_ptr() + 4 * C)
             if trains_qkv1:
                 bgemm(dqkv, n1, 3 * C, C, rows, lda=3 * C, ldb=C, a_t=True, b_t=True, c_f32=self._g(t + ".attn1.to_q.weight"), ldc=C)
             dn1 = torch.empty(rows, C, dtype=torch.float32, device=dev)
