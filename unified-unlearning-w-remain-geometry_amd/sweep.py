@@ -186,6 +186,7 @@ class FlatAdam:
                 import torch as _t
                 rngs, quant = split["ranges"], split.get("quant")
                 side = split.get("stream")
+                assert self.g2 is None, "split= sweeps read one gradient arena: the block-range launches below do not take g2"
                 # the first `head` ranges stay on the current stream (the next forward pass needs them first); with `quant` (config 5)
                 # every range goes through the per-tensor launches below, without a second stream all of them on this one
                 head = int(split.get("head", 0)) if side is not None else len(rngs)
