@@ -967,6 +967,36 @@ int sfron_ddpm_sampler_advance(const float* tseq, int steps, int32_t* step, floa
  * sfron_rows_to_image_u8 would refuse, gets bytes of 0. */
 int sfron_images_normalize_u8(const float* x, int B, int H, int W, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ classifier evaluation (classify.hip)
+ * What the ResNet-34 / ResNet-50 forward passes of DDPM/classifier_evaluation.py and SD/eval-scripts/imageclassify.py need beside
+ * sfron_conv_fwd and the GEMM.  Every entry point: SFRON_ERR_ARG before any launch for a null pointer, a non-positive extent or an
+ * operand of 2 GiB or more; 64-bit element offsets; no allocation, no synchronisation.
+ *
+ * The im2col matrix of the 7x7 / stride 2 / pad 3 stem: img uint8 [B][H][W][3] -> bf16 rows [B * Ho * Wo][k_pad], Ho = (H + 6 - 7) / 2 + 1
+ * (Wo alike).  Column (kh * 7 + kw) * 3 + c = bf16_rne((x / 255.0f - mean[c]) / std[c]) of pixel (2 ho + kh - 3, 2 wo + kw - 3), true
+ * fp32 divisions (the arithmetic of sfron_image_u8_to_rows_bf16: with mean = std = 0.5 the same bits); a pixel outside the image is 0 in
+ * NORMALISED space (Conv2d pads after Normalize), as are columns 147 .. k_pad - 1.  k_pad % 8 == 0, k_pad >= 152, rows 16-byte aligned. */
+int sfron_image_u8_patches7(const uint8_t* img, int B, int H, int W, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                            int k_pad, uint16_t* rows, void* stream);
+/* the same matrix from a float [B][3][H][W] tensor that is already normalised: bf16_rne(x) */
+int sfron_nchw_patches7(const float* x, int B, int H, int W, int k_pad, uint16_t* rows, void* stream);
+/* MaxPool2d(3, 2, 1) over fp32 rows [B * H * W][ld] (C channels; C % 4 == 0, ld % 4 == 0, x 16-byte aligned) -> [B * Ho * Wo][C] as bf16
+ * (y_bf16), fp32 (y_f32) or both (either may be NULL, not both): the maximum over the IN-BOUNDS pixels of the window (padding is -inf,
+ * not 0), then, with relu != 0, clamped at 0 -- ReLU and the pool commute. */
+int sfron_relu_maxpool3s2(const float* x, int ld, int B, int H, int W, int C, int relu, uint16_t* y_bf16, float* y_f32, void* stream);
+/* max(x, 0) of fp32 rows [rows][ld] (C % 4 == 0, ld % 4 == 0): y_f32 [rows][ld] (may be x), y_bf16 [rows][C], or both. -0.0 stays -0.0. */
+int sfron_relu_rows(const float* x, int ld, int64_t rows, int C, uint16_t* y_bf16, float* y_f32, void* stream);
+/* AdaptiveAvgPool2d(1) + Linear in fp32: pooled[b][c] = (sum over the HW rows of sample b, in row order) / HW; logits[b][n] =
+ * sum_c w[n][c] * pooled[b][c] + bias[n] (bias may be NULL).  x fp32 rows [B * HW][ld], w fp32 [n_cls][C] (C % 4 == 0, w and pooled 16-byte
+ * aligned), pooled fp32 [B][C] (written), logits fp32 [B][n_cls].  A fixed summation order: the same call gives the same bits. */
+int sfron_pool_fc(const float* x, int ld, int B, int HW, int C, const float* w, const float* bias, int n_cls, float* pooled, float* logits,
+                  void* stream);
+/* Per row of logits [B][ld] (n_cls used), one workgroup each: probs [B][n_cls] = softmax; entropy [B] = -sum p log p where a term with
+ * p == 0 counts as 0; p_target [B] = p[target]; argmax [B]; topk_p / topk_i [B][topk] = the topk <= 8 largest probabilities and their
+ * indices, descending, equal values by the lower index.  Every output is optional (NULL), topk_p and topk_i only when topk == 0. */
+int sfron_classify_metrics(const float* logits, int ld, int B, int n_cls, int target, int topk, float* probs, float* entropy, float* p_target,
+                           int32_t* argmax, float* topk_p, int32_t* topk_i, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

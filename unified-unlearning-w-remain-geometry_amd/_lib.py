@@ -317,6 +317,14 @@ _PROTOS.update({
     "sfron_ddpm_sampler_advance": (c_int, [_P, c_int, _P, _P, c_int, _S]),
     "sfron_images_normalize_u8": (c_int, [_P, c_int, c_int, c_int, _P, _S]),
 })
+_PROTOS.update({           # csrc/classify.hip: the ResNet evaluators
+    "sfron_image_u8_patches7": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_int, _P, _S]),
+    "sfron_nchw_patches7": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _S]),
+    "sfron_relu_maxpool3s2": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _S]),
+    "sfron_relu_rows": (c_int, [_P, c_int, c_int64, c_int, _P, _P, _S]),
+    "sfron_pool_fc": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _S]),
+    "sfron_classify_metrics": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _S]),
+})
 ERR_ARG = 1001                  # SFRON_ERR_ARG
 ERR_UNSUPPORTED = 1002         # SFRON_ERR_UNSUPPORTED (csrc/common.h)
 

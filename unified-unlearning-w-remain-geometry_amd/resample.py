@@ -118,9 +118,11 @@ def resized_size(w, h, size):
     return (new_short, new_long) if w <= h else (new_long, new_short)
 
 
-def center_crop_offsets(h, w, size):
-    """(top, left) of torchvision.transforms.CenterCrop(size) on an h x w image that is at least size x size."""
-    return int(round((h - size) / 2.0)), int(round((w - size) / 2.0))
+def center_crop_offsets(h, w, size, crop=None):
+    """(top, left) of torchvision.transforms.CenterCrop(crop) on an h x w image that is at least crop x crop; ``crop`` defaults to
+    ``size``, the Resize(size) -> CenterCrop(size) of the SD scripts (Resize(232) -> CenterCrop(224) passes crop=224)."""
+    crop = size if crop is None else int(crop)
+    return int(round((h - crop) / 2.0)), int(round((w - crop) / 2.0))
 
 
 def _filter_name(interpolation):
@@ -131,7 +133,7 @@ def _filter_name(interpolation):
 
 
 # ------------------------------------------------------------------------------------------------ the transform on the host
-def sd_transform(pil_image, size, interpolation="bicubic"):
+def sd_transform(pil_image, size, interpolation="bicubic", crop=None):
     """get_transform of SD/train-scripts/dataset.py up to the bytes: Resize(size, interpolation) -> CenterCrop(size) -> convert("RGB"),
     as uint8 [size, size, 3] on the host with Pillow.  The yardstick of ``sd_transform_gpu`` and its route for the modes the device does
     not take."""
@@ -140,8 +142,9 @@ def sd_transform(pil_image, size, interpolation="bicubic"):
     nw, nh = resized_size(w, h, size)
     if (nw, nh) != (w, h):
         img = img.resize((nw, nh), _PIL_FILTER[_filter_name(interpolation)])
-    top, left = center_crop_offsets(nh, nw, size)
-    img = img.crop((left, top, left + size, top + size)).convert("RGB")
+    crop = size if crop is None else int(crop)
+    top, left = center_crop_offsets(nh, nw, size, crop)
+    img = img.crop((left, top, left + crop, top + crop)).convert("RGB")
     return np.array(img, dtype=np.uint8)                   # (a copy the caller owns: np.asarray of a PIL image is read-only)
 
 
@@ -176,12 +179,14 @@ def image_resample_u8(src, Hs, Ws, tx, ty, tmp, dst, tmp_bytes=None):
                                               p(dst), stream_ptr())
 
 
-def window_tables(w, h, size, interpolation="bicubic"):
-    """(tx, ty) of the size x size centre-crop window of the resize of a w x h image (``resized_size`` + ``center_crop_offsets``)."""
+def window_tables(w, h, size, interpolation="bicubic", crop=None):
+    """(tx, ty) of the crop x crop (default size x size) centre-crop window of the resize of a w x h image (``resized_size`` +
+    ``center_crop_offsets``)."""
     name = _filter_name(interpolation)
+    crop = size if crop is None else int(crop)
     nw, nh = resized_size(w, h, size)
-    top, left = center_crop_offsets(nh, nw, size)
-    return resample_tables(w, nw, name, left, size), resample_tables(h, nh, name, top, size)
+    top, left = center_crop_offsets(nh, nw, size, crop)
+    return resample_tables(w, nw, name, left, crop), resample_tables(h, nh, name, top, crop)
 
 
 class _Staging:
