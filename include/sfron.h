@@ -214,7 +214,10 @@ typedef struct sfron_gemm_desc {
   int split_k;                       /* > 1 (EPI_F32 only, no bias): split s writes its partial product to
                                         c_f32 + s * split_stride; sum the slabs with sfron_reduce_chunks */
   long split_stride;
-  int tile_hint;                     /* 0 = auto; -1 = generic kernel; fast tiles 1 = 128x128, 2 = 256x192, 3 = 256x256, 4 = 384x192 */
+  int tile_hint;                     /* 0 = auto; -1 = generic kernel; fast tiles 1 = 128x128, 2 = 256x192, 3 = 256x256, 4 = 384x192; further
+                                        tuning values in csrc/gemm.hip pick_fast_tile (tests/test_gemm_paths_cpu.py lists them).  Every accepted
+                                        value gives the same product: a tile that does not fit the shape, and any unknown value, runs the
+                                        generic kernel.  21 / 22 (timing ablations that skip work) exist in the SFRON_DEBUG_KNOBS build only. */
   float* a_rowsum;                   /* weight-gradient layout only (a_transposed = b_transposed = 1, EPI_F32, no split): fp32 [M],
                                         a_rowsum[m] = sum_k op(A)[m][k] -- the bias gradient sum_rows dY of the same nn.Linear
                                         (DiT/models.py:108-121 backward), taken from the dY tiles the GEMM already holds in LDS
@@ -377,7 +380,9 @@ int sfron_fp8_wgrad(const sfron_fp8_wgrad_desc* desc /* HOST pointer */, void* s
  * and backward.  Activations are NHWC: a [batch * H * W][C] row-major matrix (bf16 where they feed a GEMM, fp32 elsewhere). */
 
 /* batched GEMM on the generic 128x128 tile: C[z] = alpha * op(A[z]) op(B[z]) (+ bias) (+ resid) (+ per-sample row vector),
- * z < batch, operands advanced by the element strides; layouts as sfron_gemm_desc.  Exactly one of c_bf16 / c_f32 is set. */
+ * z < batch, operands advanced by the element strides; layouts as sfron_gemm_desc.  Exactly one of c_bf16 / c_f32 is set.
+ * a_transposed = 1 needs b_transposed = 1: A^T against a B that is not transposed is refused with SFRON_ERR_ARG, like every
+ * other rule on the arguments (N % 4, lda / ldb / strides % 8, 16-byte aligned operands, each matrix below 2 GiB). */
 typedef struct sfron_bgemm_desc {
   const uint16_t* A; const uint16_t* B;
   int M, N, K, lda, ldb;

@@ -84,6 +84,10 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, c1, c0));
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
+// GELU' forms 1 - s as e * s.  Below x = -10.06 the exponent argument passes 128: e = exp2(..) = +inf, s = 1 / (1 + e) = 0, and e * s would
+// be NaN where GELU' is 0 (a NaN into dX; code 0 = -0.15 in the one-byte form).  The e of that product alone is therefore held at 2^126:
+// min(inf, 2^126) * 0 = 0 and GELU' = s = 0.  s, and with it GELU(x) = x s, is untouched; nothing changes for x >= -10 (e <= 2^126).
+constexpr float GELU_E_MAX = 0x1p126f;
 __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const float c0 = -2.0f * 1.4426950408889634f * k0, c1 = c0 * k1;
@@ -91,13 +95,16 @@ __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(t, c1, c0));
   const float s = __builtin_amdgcn_rcpf(1.0f + e);                       // 0.5*(1+tanh u)
   const float du2 = __builtin_fmaf(t, 6.0f * k0 * k1, 2.0f * k0);        // 2 du/dx
-  return __builtin_fmaf((x * s) * (e * s), du2, s);                      // s + x s (1-s) 2 du
+  return __builtin_fmaf((x * s) * (__builtin_fminf(e, GELU_E_MAX) * s), du2, s);     // s + x s (1-s) 2 du
 }
 // The same two functions on the 4 accumulator values of a lane, written with vector operations so that hipcc emits the PACKED forms
 // (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two values per VALU slot): the fused GELU epilogues are VALU-bound -- 5.8 of the 30 us an
 // fc1 workgroup lives, 6.0 of 25.8 in the fc2 dgrad (tools/bench_gemm.py phases, profiles/r04_gemm_phases.txt).  Operation for
 // operation the scalar sequence above: bit-identical results.
 __device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
+__device__ __forceinline__ f32x4 gelu_e_held4(f32x4 e) {
+  return f32x4{__builtin_fminf(e[0], GELU_E_MAX), __builtin_fminf(e[1], GELU_E_MAX), __builtin_fminf(e[2], GELU_E_MAX), __builtin_fminf(e[3], GELU_E_MAX)};
+}
 __device__ __forceinline__ f32x4 gelu_tanh4(f32x4 x) {
   const float c0 = -2.0f * 1.4426950408889634f * 0.7978845608028654f, c1 = c0 * 0.044715f;
   const f32x4 a = x * __builtin_elementwise_fma(x * x, splat4(c1), splat4(c0));
@@ -115,7 +122,7 @@ __device__ __forceinline__ f32x4 gelu_tanh_grad4(f32x4 x) {
   const f32x4 d = splat4(1.0f) + e;
   const f32x4 s = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
   const f32x4 du2 = __builtin_elementwise_fma(t, splat4(6.0f * k0 * k1), splat4(2.0f * k0));
-  return __builtin_elementwise_fma((x * s) * (e * s), du2, s);
+  return __builtin_elementwise_fma((x * s) * (gelu_e_held4(e) * s), du2, s);
 }
 // GELU and its derivative from ONE exp / rcp pair (operation for operation gelu_tanh4 and gelu_tanh_grad4: the same bits as either alone).
 __device__ __forceinline__ void gelu_tanh_both4(f32x4 x, f32x4& y, f32x4& dy) {
@@ -128,7 +135,7 @@ __device__ __forceinline__ void gelu_tanh_both4(f32x4 x, f32x4& y, f32x4& dy) {
   const f32x4 s = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
   const f32x4 du2 = __builtin_elementwise_fma(t, splat4(6.0f * k0 * k1), splat4(2.0f * k0));
   y = x * s;
-  dy = __builtin_elementwise_fma(y * (e * s), du2, s);
+  dy = __builtin_elementwise_fma(y * (gelu_e_held4(e) * s), du2, s);
 }
 // GELU'(x) as ONE byte (round 6: the second output of fc1 + GELU, sfron_gemm_desc SFRON_EPI_GELU_Q / SFRON_EPI_DGELU_Q).  GELU'_tanh takes
 // values in [-0.1290, 1.1290]; code = round((g' + 0.15) * 196) in 0 .. 251, g' = code / 196 - 0.15: a step of 0.0051, i.e. at most 0.0026 of

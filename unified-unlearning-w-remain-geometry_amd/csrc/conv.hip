@@ -2280,6 +2280,7 @@ int sfron_bgemm_bf16(const sfron_bgemm_desc* d, void* stream) {
   SFRON_CHECK_ARG(d && d->A && d->B && d->M > 0 && d->N > 0 && d->K > 0 && d->batch >= 1);
   SFRON_CHECK_ARG(d->N % 4 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && (((uintptr_t)d->A | (uintptr_t)d->B) & 15) == 0);
   SFRON_CHECK_ARG(d->stride_a % 8 == 0 && d->stride_b % 8 == 0 && d->stride_c % 4 == 0);
+  SFRON_CHECK_ARG(!d->a_transposed || d->b_transposed);          // no kernel reads A^T against a B that is not transposed
   if (!d->a_transposed || !d->b_transposed) SFRON_CHECK_ARG(d->K % 8 == 0);
   if (d->a_transposed) SFRON_CHECK_ARG(d->M % 8 == 0);
   if (d->b_transposed) SFRON_CHECK_ARG(d->N % 8 == 0);

@@ -1768,7 +1768,11 @@ inline int pick_fast_tile(const GemmArgs& g, int force, int transposed_operands)
     if (transposed_operands <= 1 && tile_fits(g, 2)) return 42;      // (round 5: the forward layout too -- few-tile products of a small batch)
     return 0;
   }
-  if (force == 21 || force == 22) return tile_fits(g, 2) ? force : 0;            // timing ablations of tile 2
+#ifdef SFRON_DEBUG_KNOBS
+  // timing ablations of tile 2 (no MFMAs / no loads after the first k-tile): they return SFRON_OK with a WRONG product, so only the debug build
+  // (tools/ A-B runs) reaches them; the product build takes the hint for the generic kernel like any other unknown value above 10
+  if (force == 21 || force == 22) return tile_fits(g, 2) ? force : 0;
+#endif
   if (force == 32 || force == 35 || force == 36) return tile_fits(g, force - 30) ? force : 0;   // hand-pipelined variants of tiles 2, 5, 6
   if (force == 42 || force == 45) return tile_fits(g, force - 40) ? force : 0;                  // ... with the interleaved schedule
   if (force == 55) return tile_fits(g, 5) ? force : 0;                                          // ... and three LDS slots
