@@ -479,6 +479,8 @@ int sfron_rows_to_nchw(const float* rows, int ld, int B, int C, int HW, float* x
  *              cells are byte 0 and are written by the launch with b0 == 0.  n == 1 gives the bare H x W image.
  * Hc * Wc * 3 (or B * H * W * 3) < 2^31. */
 enum { SFRON_IMAGE_SAVE_IMAGE = 0, SFRON_IMAGE_ROUND = 1 };
+/*   SFRON_IMAGE_TRUNC (DiT/sample_ddp.py:132; lo, hi unused):  u = trunc(clamp(127.5f * x + 128.0f, 0, 255))   (product, then sum) */
+enum { SFRON_IMAGE_TRUNC = 2 };
 int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int mode, float lo, float hi, int nrow, int padding, int b0, int n,
                            uint8_t* out, void* stream);
 
@@ -971,6 +973,47 @@ int sfron_ddpm_sampler_advance(const float* tseq, int steps, int32_t* step, floa
  * launched).  An image for which hi > lo does not hold after that rule (a constant image with |lo| >= 128, or no finite value), which
  * sfron_rows_to_image_u8 would refuse, gets bytes of 0. */
 int sfron_images_normalize_u8(const float* x, int B, int H, int W, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------ DiT guided sampling (dit_sample.hip)
+ * One sampling step of DiT/diffusion/gaussian_diffusion.py behind ONE forward pass, with forward_with_cfg's guidance (DiT/models.py:250-266)
+ * folded in.  fp32, 64-bit element offsets, one launch.
+ *   x         [n][C][hw]
+ *   model_out [rows][2C][hw]: guided != 0: rows = 2n, row i the conditional and row i + n the null pass of sample i; else rows = n.
+ *             Channels 0..C-1 are epsilon, C..2C-1 the variance interpolation v.
+ *   t         DEVICE int64 [n]: PER-ROW indices into the sampler table (the respaced index, as for sfron_p_sample)
+ *   stab      DEVICE float [T][11]: the eight columns of sfron_p_sample's table in their order (sqrt_ac, sqrt_1m_ac, sqrt_recip_ac,
+ *             sqrt_recipm1_ac, post_coef1, post_coef2, post_logvar_clipped, log_beta), then alphas_cumprod, alphas_cumprod_prev,
+ *             alphas_cumprod_next: each the fp64 table value rounded once to fp32
+ *   noise     [n][C][hw]; may be NULL in mode DDIM with eta == 0 and in mode DDIM_REVERSE (NULL counts as zeros)
+ *   sample    [n][C][hw] (may be x: an element is read before it is written, by the same thread); sample_dup (may be NULL) receives the same
+ *             values -- the second half of the next guided model input; pred_xstart may be NULL.
+ * Guidance (guided != 0): epsilon channels < n_guided become u + s * (c - u) (c = conditional, u = null, s = cfg_scale), the expression of
+ * sfron_cfg_combine; epsilon channels >= n_guided and every variance channel are the conditional row's -- the reference's quirk of guiding
+ * three channels only, which the first half of its batch then carries.
+ * Variance, pred_xstart = sra * x - srm1 * eps and its clamp to [-1, 1] (clip_denoised) are sfron_p_sample's expressions.
+ *   SFRON_DIT_SAMPLE_DDPM          sfron_p_sample's update: sample = (c1 * pred + c2 * x) + ((t != 0) * exp(0.5 * log_var)) * noise
+ *   SFRON_DIT_SAMPLE_DDIM          ddim_sample (:513-560), in the reference's operation order:
+ *                                    eps = (sra * x - pred) / srm1                     (re-derived, also without the clamp)
+ *                                    sigma = eta * sqrt((1 - ab_prev) / (1 - ab)) * sqrt(1 - ab / ab_prev)
+ *                                    sample = (pred * sqrt(ab_prev) + sqrt(1 - ab_prev - sigma * sigma) * eps) + ((t != 0) * sigma) * noise
+ *   SFRON_DIT_SAMPLE_DDIM_REVERSE  ddim_reverse_sample (:562-598), eta must be 0:
+ *                                    sample = pred * sqrt(ab_next) + sqrt(1 - ab_next) * eps
+ * The library builds with -ffp-contract=off, so in mode DDPM the result is BIT-EQUAL, on the n rows, to sfron_cfg_combine(model_out, 2n, 2C,
+ * hw, n_guided, cfg_scale) followed by sfron_p_sample on the first n rows of x / model_out / t / noise (unguided: to sfron_p_sample alone).
+ * SFRON_ERR_ARG before any launch, outputs untouched, for: a null required pointer (noise where the mode needs one), a non-positive
+ * extent, n_guided outside [0, C], a cfg_scale or eta that is not finite, an unknown mode, mode DDIM_REVERSE with eta != 0, a pred_xstart or
+ * sample_dup that aliases x or sample (or each other), n * C * hw >= 2^31 or n > 65535 (the grid's second dimension). */
+enum { SFRON_DIT_SAMPLE_DDPM = 0, SFRON_DIT_SAMPLE_DDIM = 1, SFRON_DIT_SAMPLE_DDIM_REVERSE = 2 };
+int sfron_dit_sample_step(const float* x, const float* model_out, const int64_t* t, const float* stab, const float* noise, int n, int c,
+                          int hw, int guided, int n_guided, float cfg_scale, int mode, float eta, int clip_denoised, float* sample,
+                          float* sample_dup, float* pred_xstart, void* stream);
+/* The step counter of a DiT sampling loop, one workgroup: k = *step clamped into [0, steps); i = order[min(k + 1, steps - 1)] clamped into
+ * [0, map_len); t_idx[0 .. n) = i (the table index sfron_dit_sample_step reads at the next step); t_model[0 .. rows) = timestep_map[i] (the
+ * ORIGINAL timestep the DiT engine reads, respace.py:117-129); *step = k + 1.  order (int64 [steps]) and timestep_map (int64 [map_len])
+ * are DEVICE tables: the host uploads nothing per step.  A launch of its own behind the step kernel, for the reason given at
+ * sfron_ddpm_sampler_advance.  SFRON_ERR_ARG before any launch for a null pointer or a non-positive extent. */
+int sfron_dit_sampler_advance(const int64_t* order, const int64_t* timestep_map, int steps, int map_len, int32_t* step, int64_t* t_idx, int n,
+                              int64_t* t_model, int rows, void* stream);
 
 /* ------------------------------------------------------------------ classifier evaluation (classify.hip)
  * What the ResNet-34 / ResNet-50 forward passes of DDPM/classifier_evaluation.py and SD/eval-scripts/imageclassify.py need beside

@@ -911,6 +911,7 @@ __global__ __launch_bounds__(TPB) void k_image_u8_to_rows(const uint8_t* __restr
 //   mode 0 (torchvision make_grid(normalize=True, value_range=(lo, hi)) + save_image):
 //          v = (min(max(x, lo), hi) - lo) / (hi - lo);  u = trunc(min(max(v * 255 + 0.5, 0), 255))  (v * 255, then + 0.5)
 //   mode 1 (diffusers / SD generate-images.py):  v = min(max(x / 2 + 0.5, 0), 1);  u = rint(v * 255)  (half to even)
+//   mode 2 (DiT/sample_ddp.py:132):  u = trunc(min(max(127.5 * x + 128, 0), 255))  (the product, then the sum)
 // The rows hold samples b0 .. b0+B-1 of a batch of n.  nrow == 0: out = [n][H][W][3], this launch writes its B samples.  nrow > 0: out =
 // the make_grid canvas [Hc][Wc][3] (xmaps = min(nrow, n) columns, cells (H+p) x (W+p) behind a p-pixel border, n == 1: the bare image);
 // one thread per canvas pixel, each launch writes the pixels of its own samples and the launch with b0 == 0 also the pad pixels (byte 0).
@@ -920,6 +921,12 @@ __device__ __forceinline__ uint8_t img_u8(float x, int mode, float lo, float hi)
     const float v = (c - lo) / (hi - lo);
     float t = v * 255.0f;
     t = t + 0.5f;
+    t = fminf(fmaxf(t, 0.0f), 255.0f);
+    return (uint8_t)(int)t;
+  }
+  if (mode == SFRON_IMAGE_TRUNC) {
+    float t = 127.5f * x;
+    t = t + 128.0f;
     t = fminf(fmaxf(t, 0.0f), 255.0f);
     return (uint8_t)(int)t;
   }
@@ -2580,7 +2587,7 @@ int sfron_nchw_to_rows_f32(const float* x, int B, int C, int HW, int ld, float* 
 }
 int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int mode, float lo, float hi, int nrow, int padding, int b0, int n,
                            uint8_t* out, void* stream) {
-  SFRON_CHECK_ARG(rows && out && ld >= 3 && B > 0 && H > 0 && W > 0 && (mode == SFRON_IMAGE_SAVE_IMAGE || mode == SFRON_IMAGE_ROUND));
+  SFRON_CHECK_ARG(rows && out && ld >= 3 && B > 0 && H > 0 && W > 0 && (mode == SFRON_IMAGE_SAVE_IMAGE || mode == SFRON_IMAGE_ROUND || mode == SFRON_IMAGE_TRUNC));
   SFRON_CHECK_ARG(nrow >= 0 && padding >= 0 && b0 >= 0 && n >= b0 + B && (mode != SFRON_IMAGE_SAVE_IMAGE || hi > lo));
   int xmaps = 0, pad = 0;
   int64_t Hc, Wc;

@@ -57,6 +57,7 @@ def _tables_fp64(num_timesteps=1000, use_timesteps=None):
     post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
     return dict(
         timestep_map=tmap, betas=betas, alphas_cumprod=ac,
+        alphas_cumprod_prev=ac_prev, alphas_cumprod_next=np.append(ac[1:], 0.0),          # gaussian_diffusion.py:169-170
         sqrt_alphas_cumprod=np.sqrt(ac), sqrt_one_minus_alphas_cumprod=np.sqrt(1.0 - ac),
         sqrt_recip_alphas_cumprod=np.sqrt(1.0 / ac), sqrt_recipm1_alphas_cumprod=np.sqrt(1.0 / ac - 1),
         posterior_mean_coef1=betas * np.sqrt(ac_prev) / (1.0 - ac),
@@ -68,6 +69,11 @@ def _tables_fp64(num_timesteps=1000, use_timesteps=None):
 _TAB_ORDER = ["sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod",
               "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
               "posterior_log_variance_clipped", "log_betas"]
+
+
+# the sampler table of sfron_dit_sample_step: the eight columns above in their order, then these three (include/sfron.h)
+_SAMPLER_TAB_ORDER = _TAB_ORDER + ["alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next"]
+_STEP_MODES = {"ddpm": _lib.DIT_SAMPLE_DDPM, "ddim": _lib.DIT_SAMPLE_DDIM, "ddim_reverse": _lib.DIT_SAMPLE_DDIM_REVERSE}
 
 
 class _WrappedModel:
@@ -93,6 +99,9 @@ class GaussianDiffusion:
         self.map_tensor = torch.tensor(self.timestep_map, dtype=torch.int64, device=device)
         packed = np.stack([self.tables[k] for k in _TAB_ORDER], axis=1).astype(np.float32)
         self.tab = torch.from_numpy(packed).to(device).contiguous()
+        # a table of its own, [T][11]: the loss / p_sample kernels index ``tab`` by 8
+        spacked = np.stack([self.tables[k] for k in _SAMPLER_TAB_ORDER], axis=1).astype(np.float32)
+        self.sampler_tab = torch.from_numpy(spacked).to(device).contiguous()
 
     def _wrap_model(self, model):
         if self._identity_map or isinstance(model, _WrappedModel):
@@ -178,6 +187,79 @@ class GaussianDiffusion:
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
                                                     progress, step_noise):
+            pass
+        return final["sample"]
+
+
+    # ------------------------------------------------------------------ DDIM (gaussian_diffusion.py:513-680)
+    def sample_step(self, x, model_output, t, mode, noise=None, eta=0.0, clip_denoised=True, cfg_scale=None, n_guided=3, sample=None,
+                    sample_dup=None, pred_xstart=None):
+        """One sfron_dit_sample_step launch.  x [n, C, ...], t int64 [n] (table indices, per row), model_output [n, 2C, ...], or
+        [2n, 2C, ...] with ``cfg_scale`` given (row i conditional, row i + n null: the guidance of forward_with_cfg on the first
+        ``n_guided`` epsilon channels).  mode "ddpm" | "ddim" | "ddim_reverse".  sample (may be x) / sample_dup / pred_xstart: output
+        tensors, sample allocated when None.  Returns sample."""
+        n, c = x.shape[0], x.shape[1]
+        guided = cfg_scale is not None
+        assert model_output.shape[0] == (2 * n if guided else n) and model_output.shape[1] == 2 * c
+        if sample is None:
+            sample = torch.empty_like(x)
+        check(_lib.lib().sfron_dit_sample_step(ptr(x), ptr(model_output), ptr(t), ptr(self.sampler_tab), ptr(noise), n, c, x[0, 0].numel(),
+                                               int(guided), int(n_guided), float(cfg_scale) if guided else 1.0, _STEP_MODES[mode],
+                                               float(eta), int(bool(clip_denoised)), ptr(sample), ptr(sample_dup), ptr(pred_xstart),
+                                               stream_ptr()), f"dit_sample_step({mode})")
+        return sample
+
+    def _ddim_step(self, mode, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, noise):
+        if denoised_fn is not None or cond_fn is not None:
+            raise NotImplementedError("denoised_fn / cond_fn are not used by the unlearning scripts")
+        x = x.contiguous().float()
+        t = t.contiguous()
+        model_output = self._wrap_model(model)(x, t, **(model_kwargs or {}))
+        if isinstance(model_output, tuple):
+            model_output = model_output[0]
+        n, c = x.shape[0], x.shape[1]
+        assert model_output.shape == (n, 2 * c, *x.shape[2:])
+        if mode == "ddim" and noise is None and eta != 0.0:
+            noise = torch.randn_like(x)
+        pred = torch.empty_like(x)
+        mo = model_output.contiguous().float()                              # named: temporaries must outlive the launch
+        nz = None if noise is None or mode == "ddim_reverse" else noise.contiguous().float()
+        sample = self.sample_step(x, mo, t, mode, noise=nz, eta=eta, clip_denoised=clip_denoised, pred_xstart=pred)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, noise=None):
+        """Reference signature (gaussian_diffusion.py:513); ``noise`` (optional) replaces the reference's ``th.randn_like(x)`` draw.  With
+        eta == 0 and no ``noise`` nothing is drawn (the reference draws and multiplies by sigma = 0)."""
+        return self._ddim_step("ddim", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, noise)
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
+        """Reference signature (gaussian_diffusion.py:562): x_{t+1} from x_t by the reverse ODE."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        return self._ddim_step("ddim_reverse", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, None)
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                     device=None, progress=False, eta=0.0, step_noise=None):
+        device = device if device is not None else self.tab.device
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        indices = list(range(self.num_timesteps))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for k, i in enumerate(indices):
+            t = torch.tensor([i] * shape[0], device=device)
+            with torch.no_grad():
+                out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                       model_kwargs=model_kwargs, eta=eta, noise=None if step_noise is None else step_noise[k])
+            yield out
+            img = out["sample"]
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, eta=0.0, step_noise=None):
+        """Reference signature (gaussian_diffusion.py:600); ``step_noise[k]`` optionally fixes the k-th per-step draw."""
+        final = None
+        for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                                                       progress, eta, step_noise):
             pass
         return final["sample"]
 

@@ -19,9 +19,14 @@ _MODES = {"save_image": 0, "round": 1}          # include/sfron.h SFRON_IMAGE_SA
 FORGET_CLASS_LABELS = (207, 360, 387, 972, 89, 979, 417, 279, 270, 980)
 
 
+IMAGE_TRUNC = 2                                  # SFRON_IMAGE_TRUNC: the bytes of DiT/sample_ddp.py:132 ("trunc")
+
+
 def image_mode(mode):
+    if mode == "trunc":
+        return IMAGE_TRUNC
     if mode not in _MODES:
-        raise ValueError(f"mode must be one of {sorted(_MODES)}, got {mode!r}")
+        raise ValueError(f"mode must be one of {sorted(_MODES) + ['trunc']}, got {mode!r}")
     return _MODES[mode]
 
 
@@ -97,16 +102,35 @@ class _StepNoise:
 
 @torch.no_grad()
 def sample_visualization(model, diffusion, decoder, latent_size, train_steps, checkpoint_dir, class_labels=FORGET_CLASS_LABELS,
-                         cfg_scale=4.0, generator=None, nrow=5):
+                         cfg_scale=4.0, generator=None, nrow=5, native=False):
     """DiT/forget.py:114-145 on the GPU: guided ancestral sampling of ``class_labels`` (z doubled, null labels, clip_denoised=False),
     the first half decoded (``samples / 0.18215``), written as ``{train_steps:07d}_sample.png`` under ``checkpoint_dir`` (make_grid
     nrow=5, normalize=True, value_range=(-1, 1)).  Returns the uint8 grid [Hc, Wc, 3] on the device.
 
     ``generator``: every draw (z, then each step's noise) comes from it and the global RNG is left alone; None draws as the reference
     does.  The model runs on an engine of its own over the same parameter arenas, so a DiTSFRon runner's engine, workspaces, streams and
-    batch size are as they were; a sweep the runner left in flight is drained first (the sampler reads the parameters)."""
+    batch size are as they were; a sweep the runner left in flight is drained first (the sampler reads the parameters).
+
+    ``native=True`` runs the loop through ``dit_sample.DiTSampler`` (one forward pass, one sfron_dit_sample_step and one
+    sfron_dit_sampler_advance per step, no host tensor per step): the same draws from ``generator`` and the same grid bytes for
+    ``cfg_scale > 1`` (at or below 1 the sampler runs unguided at batch n, where the default path still mixes at batch 2n)."""
     dev = model.engine.device
     n = len(class_labels)
+    if native:
+        from .dit_sample import DiTSampler
+        shape = (n, model.in_channels, latent_size, latent_size)
+        if generator is not None:
+            z = torch.randn(shape, generator=generator, device=generator.device).to(dev)
+        else:
+            z = torch.randn(*shape, device=dev)
+        y = torch.tensor(list(class_labels), device=dev)
+        try:
+            samples = DiTSampler(model, diffusion, cfg_scale, clip_denoised=False).sample(z, y, generator=generator)
+            grid = decoder.decode_u8(samples, 0.18215, "save_image", nrow=nrow)
+        finally:
+            model.train()                # what the default path leaves behind (forget.py:145)
+        write_png(grid, os.path.join(checkpoint_dir, f"{train_steps:07d}_sample.png"))
+        return grid
     eng = model.engine
     eng.drain_sweep()
     model.eval()                         # important! This disables randomized embedding dropout

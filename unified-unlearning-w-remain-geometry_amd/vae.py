@@ -805,8 +805,9 @@ class VAEDecoder(_VAENet):
     @torch.no_grad()
     def decode_u8(self, z, scale=0.18215, mode="save_image", nrow=0, padding=2, value_range=(-1.0, 1.0)):
         """uint8 on the device.  mode "save_image": torchvision save_image(normalize=True, value_range) bytes; "round": the diffusers /
-        SD generate-images.py bytes ((x / 2 + 0.5).clamp(0, 1) * 255, rounded half to even).  nrow == 0: [B, H, W, 3]; nrow > 0: the
-        make_grid(nrow, padding) canvas [Hc, Wc, 3] (images.grid_geometry)."""
+        SD generate-images.py bytes ((x / 2 + 0.5).clamp(0, 1) * 255, rounded half to even); "trunc": the DiT/sample_ddp.py:132 bytes
+        (clamp(127.5 * x + 128, 0, 255) truncated; value_range unused).  nrow == 0: [B, H, W, 3]; nrow > 0: the make_grid(nrow, padding)
+        canvas [Hc, Wc, 3] (images.grid_geometry)."""
         from .images import grid_geometry, image_mode
         if self.out_ch != 3:
             raise ValueError("decode_u8 writes RGB: out_ch must be 3")
