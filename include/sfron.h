@@ -375,7 +375,7 @@ typedef struct sfron_fp8_wgrad_desc {
 int sfron_fp8_wgrad_supported(int N, int K, int M);
 int sfron_fp8_wgrad(const sfron_fp8_wgrad_desc* desc /* HOST pointer */, void* stream);
 
-/* ------------------------------------------------------------------ convolutional U-Net blocks (conv.hip)
+/* ------------------------------------------------------------------ convolutional U-Net blocks (conv.hip, groupnorm.hip, rows.hip)
  * Replaces the Conv2d / GroupNorm / bmm-softmax sequences of DDPM/models/diffusion.py:43-192,283-413 (Conditional_Model) forward
  * and backward.  Activations are NHWC: a [batch * H * W][C] row-major matrix (bf16 where they feed a GEMM, fp32 elsewhere). */
 

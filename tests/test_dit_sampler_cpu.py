@@ -64,7 +64,7 @@ def _step_args(**kw):
     dict(mode=2, eta=0.5),                                                                                 # the reverse ODE is eta == 0 only
     dict(pred=_P[0]), dict(pred=_P[5]), dict(dup=_P[0]), dict(dup=_P[5]), dict(pred=_P[6]),                # only sample may alias x
     dict(n=1 << 12, c=1 << 10, hw=1 << 9), dict(n=65536, c=1, hw=1),                                      # an int product / the grid
-], ids=lambda b: ",".join(f"{k}={v}" for k, v in b.items()))
+], ids=lambda b: ",".join(f"{k}={'P%d' % _P.index(v) if v in _P else v}" for k, v in b.items()))   # a buffer by its index: an address differs per run
 def test_step_refusals_come_before_any_launch(bad):
     from sfron import _lib
     assert _lib.lib().sfron_dit_sample_step(*_step_args(**bad)) == _lib.ERR_ARG

@@ -1,4 +1,4 @@
-"""The convolution, GroupNorm, batched-GEMM and softmax kernels of csrc/conv.hip at the shapes the KL-f8 VAE runs them at (vae.py): 256 and
+"""The convolution, GroupNorm, batched-GEMM and softmax kernels of csrc/conv.hip, groupnorm.hip and rows.hip at the shapes the KL-f8 VAE runs them at (vae.py): 256 and
 512 px images, 65 536 .. 262 144 pixels per sample, non-square crops, T = 1024 / 4096 single-head attention, operands just under 2 GiB --
 and the 2 GiB operand rule of the C entry points from both sides.
 

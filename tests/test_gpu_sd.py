@@ -1,4 +1,4 @@
-"""GPU parity of the Stable-Diffusion path (sfron.sd_unet / sfron.sd over csrc/conv.hip) -- BASELINE config 4:
+"""GPU parity of the Stable-Diffusion path (sfron.sd_unet / sfron.sd over csrc/conv.hip, groupnorm.hip, rows.hip) -- BASELINE config 4:
 (1) the kernels the LDM UNet adds to the DDPM set -- LayerNorm (affine) forward / backward, GEGLU (erf GELU), the head-batched
     attention GEMMs with a padded context -- against torch fp32;
 (2) UNetModel forward + backward against the oracle (oracle/sd_ref.py, pinned to SD/ldm/modules/... by tests/golden/sd_unet.npz):

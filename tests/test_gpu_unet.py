@@ -1,4 +1,4 @@
-"""GPU parity of the convolutional U-Net path (csrc/conv.hip + sfron.unet) -- the DDPM Conditional_Model of BASELINE config 0:
+"""GPU parity of the convolutional U-Net path (csrc/conv.hip, groupnorm.hip, rows.hip + sfron.unet) -- the DDPM Conditional_Model of BASELINE config 0:
 (1) each kernel against torch fp32 on the same bf16-rounded inputs (implicit-GEMM convolution forward / input gradient / weight
     gradient incl. the (0,1,0,1)-pad stride-2 Downsample and the nearest-x2 Upsample forms, GroupNorm(32)+swish+dropout forward /
     backward, batched GEMM + softmax of the single-head AttnBlock);

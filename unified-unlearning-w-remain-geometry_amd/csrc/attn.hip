@@ -19,15 +19,13 @@
 // head_dim 64 -> 128-B image rows, 2 k-steps, 4 d-tiles; head_dim 72 (DiT-XL) -> 192-B rows (96 columns,
 // zero padded), 3 k-steps, 5 d-tiles.
 #include "common.h"
-#include <utility>
+#include "tile.h"
 #include "../../include/sfron.h"
 
 namespace {
 
 constexpr int NT = 256, NWAVE = 4, NSLOT = 3;
 constexpr float LOG2E = 1.4426950408889634f;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 // chunk-index XOR of image row r (bank rules of MI355X_MICROARCH.md section LDS; both the ds_read_b128 row
 // fragments and the transposed reads are conflict-free):
@@ -86,8 +84,6 @@ template <int HDP, int NTHR, int IMG_STEP = 1> __device__ __forceinline__ void z
   }
 }
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // row fragment: lane holds X[row0 + (lane&15)][32*ks + 8*(lane>>4) + 0..7]
 template <int HDP> __device__ __forceinline__ bf16x8 frag_rows(const __bf16* img, int row0, int ks, int lane) {
   return *reinterpret_cast<const bf16x8*>(img + aoff<HDP>(row0 + (lane & 15), ks * 4 + (lane >> 4)));
@@ -103,30 +99,6 @@ template <int HDP> __device__ __forceinline__ bf16x8 frag_cols_perm(const __bf16
   bf16x8 r;
   r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
   r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
-// The same column fragment through inline asm.  While an LDS-DMA is in flight hipcc drains vmcnt(0) in front of every
-// ds_read_tr16_b64 BUILTIN (it cannot prove the DMA does not alias it), which would serialise the 3-slot ring;
-// an asm read is invisible to that bookkeeping.  The caller must run lds_reads_done() before using the result.
-__device__ __forceinline__ unsigned lds_addr(const __bf16* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)(const void*)p;
-}
-__device__ __forceinline__ bf16x4 asm_read_tr(unsigned addr) {
-  bf16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-__device__ __forceinline__ void lds_reads_done() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int OFF> __device__ __forceinline__ bf16x4 asm_read_tr_off(unsigned addr) {
-  bf16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
   return r;
 }
 // Permuted column fragments (frag_cols_perm) as base register + immediate: for a lane, the chunk swizzle of its rows
@@ -149,13 +121,10 @@ template <int HDP, int DT, int S2> __device__ __forceinline__ bf16x8 col_frag(co
   const bf16x4 hi = asm_read_tr_off<ColPerm<HDP>::imm(DT, S2, 1)>(a[ColPerm<HDP>::sel(DT)]);
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
-// (register-constraint asm lives in __device__ helpers: inside a __global__ body the host pass rejects the "v" constraint)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, __bf16* dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t*)dst, 16, voff, soff, 0, 0);
-}
 __device__ __forceinline__ void asm_write_b64(unsigned addr, bf16x4 v) {
   asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
+// frag_cols_perm through the asm reads of tile.h (the builtin would serialise the 3-slot ring); the caller runs lds_reads_done()
 template <int HDP> __device__ __forceinline__ bf16x8 frag_cols_perm_asm(const __bf16* img, int rbase, int col0, int lane) {
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const int ch = (col0 >> 3) + (p >> 1);

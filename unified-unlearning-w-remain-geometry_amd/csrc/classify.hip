@@ -16,7 +16,7 @@ inline int cgrid(int64_t n, int per_block = CTPB) {
 }
 
 // ---- the stem's im2col ----------------------------------------------------------------------------------------------------------------
-// ToTensor + Normalize on the fly: bf16_rne((x / 255.0f - mean[c]) / std[c]), the arithmetic of k_image_u8_to_rows (conv.hip)
+// ToTensor + Normalize on the fly: bf16_rne((x / 255.0f - mean[c]) / std[c]), the arithmetic of k_image_u8_to_rows (rows.hip)
 struct SrcU8 {
   const uint8_t* img; int H, W; float m0, m1, m2, s0, s1, s2;
   __device__ __forceinline__ float at(int64_t b, int c, int h, int w) const {

@@ -164,6 +164,30 @@ __device__ __forceinline__ float silu_grad(float x) {
   return s * (1.0f + x * (1.0f - s));
 }
 
+// four fp32 -> four OCP e4m3fn bytes, RNE, saturating at +-448 (little endian: a in bits 0..7)
+constexpr float E4M3_MAX = 448.0f;
+__device__ __forceinline__ float sat8(float x) { return fminf(fmaxf(x, -E4M3_MAX), E4M3_MAX); }
+__device__ __forceinline__ uint32_t pack_e4m3(float a, float b, float c, float d) {
+  int v = 0;
+  v = __builtin_amdgcn_cvt_pk_fp8_f32(sat8(a), sat8(b), v, false);
+  v = __builtin_amdgcn_cvt_pk_fp8_f32(sat8(c), sat8(d), v, true);
+  return (uint32_t)v;
+}
+// a buffer descriptor that covers exactly `bytes` from p (one row: a lane past its end loads zeros and its stores are dropped)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+// torchvision make_grid(normalize=True, value_range=(lo, hi)) + save_image byte (SFRON_IMAGE_SAVE_IMAGE), every step a separately rounded
+// fp32 op:  v = (min(max(x, lo), hi) - lo) / (hi - lo);  u = trunc(min(max(v * 255 + 0.5, 0), 255))  (v * 255, then + 0.5)
+__device__ __forceinline__ uint8_t save_image_u8(float x, float lo, float hi) {
+  const float c = fminf(fmaxf(x, lo), hi);
+  const float v = (c - lo) / (hi - lo);
+  float t = v * 255.0f;
+  t = t + 0.5f;
+  t = fminf(fmaxf(t, 0.0f), 255.0f);
+  return (uint8_t)(int)t;
+}
+
 
 // ---- 16-byte epilogue accesses for the D^T accumulator layout (MI355X guide T21) ------------------------------------------------
 // After an MFMA 16x16 issued as D^T = B^T A^T a lane holds row (lane & 15), columns 4 g .. 4 g + 3 (g = lane >> 4) of a 16 x 16 tile:

@@ -1,12 +1,12 @@
-// Convolutional U-Net building blocks (DDPM Conditional_Model; the same blocks serve the LDM UNetModel).
+// Convolutions of the U-Net building blocks (DDPM Conditional_Model; the same blocks serve the LDM UNetModel) and the batched GEMM.
 //
 // Replaces, for /root/reference/DDPM/models/diffusion.py:
 //   Conv2d 3x3 / 1x1 forward, input gradient and weight gradient (:49-82 Upsample / Downsample, :85-145 ResnetBlock,
 //   :148-192 AttnBlock, :283-327 conv_in / conv_out)              -> k_bgemm: implicit-GEMM convolution on NHWC bf16
-//   GroupNorm(32, eps 1e-6) (+ swish, + dropout) forward / backward (:43-46,38-40,126-131)   -> k_gn_fwd / k_gn_bwd
-//   single-head attention bmm / softmax (:168-186)                -> batched k_bgemm + k_softmax_fwd / k_softmax_bwd
+//   single-head attention bmm (:168-186)                          -> batched k_bgemm (its softmax: rows.hip)
 //   nearest-neighbour upsampling (:56-57) and the (0,1,0,1) pad + stride-2 conv (:76-80) are address arithmetic of the
-//   im2col loader (no copies); get_timestep_embedding (:17-35); classes_emb / null_classes_emb select (:370-376).
+//   im2col loader (no copies).
+// GroupNorm lives in groupnorm.hip; layouts, softmax, LayerNorm, GEGLU, casts, dropout masks and the embeddings in rows.hip.
 //
 // Activations are NHWC: a [B*H*W][C] row-major matrix, so a 3x3 convolution is the GEMM
 //   Y[p][co] = sum_{tap, ci} X[src(p, tap)][ci] * W[co][tap][ci]
@@ -16,13 +16,14 @@
 //   dgrad     A = dY (im2col, flipped taps; stride-2 convs read a zero-dilated dY),  B = W^T re-laid [Cin][taps*Cout]
 //   wgrad     A = dY^T [pixels][Cout] (transposed read),  B = X (im2col, transposed read)  -> fp32 [Cout][taps*Cin]
 // Tile 128x128x64, 4 waves, mfma_f32_16x16x32_bf16 issued as D^T = B^T A^T (lane owns 4 consecutive output columns), LDS
-// images XOR-swizzled as in gemm.hip.  The U-Net is 5 % of the DiT step's FLOPs per sample: this kernel is the generic
-// (register-staged) tile, not the LDS-DMA pipeline of gemm.hip.
+// images XOR-swizzled as in gemm.hip (tile.h).  The U-Net is 5 % of the DiT step's FLOPs per sample: k_bgemm is the generic
+// (register-staged) tile; k_cgemm / k_cgemm_t below are the LDS-DMA pipeline for the shapes that qualify.
 #include "common.h"
+#include "tile.h"
 #include <atomic>
 #include <cstdlib>
-#include <utility>
 #include "../../include/sfron.h"
+#include "unet_host.h"
 
 namespace {
 
@@ -59,22 +60,6 @@ struct BGemmArgs {
 constexpr int BM = 128, BN = 128, BK = 64, NT = 256, TILE_ELEMS = 128 * 64;
 enum { EPI_BF16 = 0, EPI_RES = 1 };
 enum { CONV_NONE = 0, CONV_A = 1, CONV_B = 2 };
-
-__device__ __forceinline__ int off_direct(int row, int ch) { return row * 64 + ((ch ^ (row & 7)) << 3); }
-__device__ __forceinline__ int swz_tr(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int off_tr(int krow, int ch) { return krow * 128 + ((ch ^ swz_tr(krow)) << 3); }
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-__device__ __forceinline__ bf16x8 frag_direct(const __bf16* img, int row, int kchunk) {
-  return *reinterpret_cast<const bf16x8*>(img + off_direct(row, kchunk));
-}
-__device__ __forceinline__ bf16x8 frag_tr(const __bf16* img, int col0, int kr0, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int ch = (col0 >> 3) + (p >> 1);
-  const int r0 = kr0 + 8 * g + q;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + off_tr(r0, ch) + 4 * (p & 1)));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + off_tr(r0 + 4, ch) + 4 * (p & 1)));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // source pixel (row index of the NHWC matrix) of output pixel (b, ho, wo) under tap `tap`; false = zero padding
 __device__ __forceinline__ bool conv_src(const ConvGeom& c, int b, int ho, int wo, int tap, int& pix) {
@@ -302,14 +287,6 @@ template __global__ void k_bgemm<true, true, EPI_RES, CONV_B>(BGemmArgs);
 // out-of-range buffer offset, for which the DMA writes zeros.  NT_ = 10 (160 columns) tiles the 320 / 640 / 1280-wide outputs of
 // the LDM UNet exactly, NT_ = 8 serves the DDPM widths (128 / 256) and ragged N (rows of B past N read as zeros through the
 // descriptor's size, the epilogue skips their columns).  Needs M % 256 == 0 and K % 64 == 0; everything else stays on k_bgemm.
-typedef __attribute__((address_space(3))) void lptr_t;
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// one wave-instruction of LDS-DMA: 64 lanes x 16 B from rsrc[voff + soff] to the lane-linear KiB at `dst` (a __device__ helper:
-// the builtin inside a kernel template's own lambda breaks hipcc's host pass)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, __bf16* dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t*)dst, 16, voff, soff, 0, 0);
-}
-
 template <int NT_>
 struct CTile {
   static constexpr int FBM = 256, FBN = NT_ * 16, NW = 8, NSLOT = 3;
@@ -506,31 +483,7 @@ template __global__ void k_cgemm<10, EPI_RES, true, 4>(BGemmArgs, unsigned, unsi
 //     SWAP : the result is stored transposed, C[q][p] (convolution weight gradient [Co][taps * Ci] with the 256-wide tile on
 //            the long (tap, ci) axis and the 128-wide one on Co: 320 / 640 / 1280 and 128 / 256 outputs tile without waste)
 // Transposed fragments are ds_read_b64_tr_b16 through inline asm (hipcc would drain vmcnt(0) before the builtin while an
-// LDS-DMA is in flight, gemm.hip); their completion is waited for explicitly.
-__device__ __forceinline__ unsigned lds_addr_of(const __bf16* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)(const void*)p;
-}
-template <int OFF>
-__device__ __forceinline__ bf16x4 asm_tr_off(unsigned addr) {
-  bf16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ bf16x8 asm_b128_off(unsigned addr) {
-  bf16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void lds_reads_done() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
+// LDS-DMA is in flight, tile.h); their completion is waited for explicitly (lds_reads_done()).
 struct TTile {
   static constexpr int FBP = 256, FBQ = 128, NW = 8, NSLOT = 3;
   static constexpr int P_ELEMS = FBP * 64, Q_ELEMS = FBQ * 64, SLOT = P_ELEMS + Q_ELEMS;
@@ -649,7 +602,7 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_cgemm_t(BGemmArgs g, unsigned
     qa[t][0] = 2 * TT::P_ELEMS + 2 * (r0 * 128 + ((chq ^ sw_lo) << 3) + 4 * (fp & 1));
     qa[t][1] = 2 * TT::P_ELEMS + 2 * ((r0 + 4) * 128 + ((chq ^ sw_hi) << 3) + 4 * (fp & 1));
   }
-  const unsigned smem_base = lds_addr_of(smem);
+  const unsigned smem_base = lds_addr(smem);
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -665,14 +618,14 @@ __global__ __launch_bounds__(512 + 64 * NL) void k_cgemm_t(BGemmArgs g, unsigned
       static_for<4>([&](auto T) {
         constexpr int t = decltype(T)::value;
         if constexpr (P_TR) {
-          const bf16x4 lo = asm_tr_off<ks * 32 * 256 * 2>(sb + pa[t][0]);
-          const bf16x4 hi = asm_tr_off<ks * 32 * 256 * 2>(sb + pa[t][1]);
+          const bf16x4 lo = asm_read_tr_off<ks * 32 * 256 * 2>(sb + pa[t][0]);
+          const bf16x4 hi = asm_read_tr_off<ks * 32 * 256 * 2>(sb + pa[t][1]);
           fpv[ks][t] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         } else {
-          fpv[ks][t] = asm_b128_off<0>(sb + pa[t][ks]);
+          fpv[ks][t] = asm_read_b128_off<0>(sb + pa[t][ks]);
         }
-        const bf16x4 lo = asm_tr_off<ks * 32 * 128 * 2>(sb + qa[t][0]);
-        const bf16x4 hi = asm_tr_off<ks * 32 * 128 * 2>(sb + qa[t][1]);
+        const bf16x4 lo = asm_read_tr_off<ks * 32 * 128 * 2>(sb + qa[t][0]);
+        const bf16x4 hi = asm_read_tr_off<ks * 32 * 128 * 2>(sb + qa[t][1]);
         fqv[ks][t] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       });
       lds_reads_done();
@@ -764,20 +717,6 @@ template __global__ void k_cgemm_t<true, true, true, EPI_RES, 4>(BGemmArgs, unsi
 
 int g_conv_loader_waves = 3;       // sfron_gemm_loader_waves(): bit 0 k_cgemm, bit 1 k_cgemm_t in the loader-wave form (0 = every wave issues its own DMA)
 namespace {
-
-constexpr int TPB = 256;
-// rows per workgroup of the row-vectorised elementwise kernels: about 2048 workgroups over (column blocks x row chunks), >= 4 rows
-inline int rows_chunk(int64_t rows, int C) {
-  const int64_t cb = (C + 255) / 256;
-  int64_t chunks = 2048 / cb; if (chunks < 1) chunks = 1;
-  int64_t r = (rows + chunks - 1) / chunks;
-  r = (r + 3) / 4 * 4;
-  return (int)(r < 4 ? 4 : r);
-}
-inline int grid_for(int64_t n, int per = TPB) {
-  int64_t b = (n + per - 1) / per;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
 
 // ---- weights: fp32 OIHW master -> bf16 GEMM operands.
 // fwd  [Co_p][taps][Ci_p]   (rows beyond Cout and channels beyond Cin are zero)
@@ -878,1024 +817,6 @@ __global__ __launch_bounds__(TPB) void k_conv_wgrad_scatter_batch(ScatterPack pa
   wgrad_scatter_block(it.dw_gemm, it.c_out, it.c_in, it.taps, it.c_in_p, it.n_slabs, it.slab_stride, it.dw_oihw, co, ci0, sh);
 }
 
-// ---- layout: NCHW fp32 image <-> NHWC rows
-__global__ __launch_bounds__(TPB) void k_nchw_to_rows(const float* __restrict__ x, int B, int C, int HW, int Cp, __bf16* __restrict__ rows) {
-  const int64_t n = (int64_t)B * HW * Cp;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int c = (int)(i % Cp); const int64_t p = i / Cp; const int hw = (int)(p % HW); const int b = (int)(p / HW);
-    rows[i] = c < C ? f2bf(x[((int64_t)b * C + c) * HW + hw]) : (__bf16)0.0f;
-  }
-}
-// uint8 HWC images (the PIL loader's arrays) -> bf16 rows [B*H*W][Cp], Cp % 8 == 0, channels 3.. zero: ToTensor + Normalize(0.5, 0.5)
-// as DiT/forget.py:200-205 computes it, (x / 255 - 0.5) / 0.5 in fp32 with true divisions, then RNE; flip[b] != 0 mirrors sample b
-// (RandomHorizontalFlip: output column w reads source column W-1-w).  One thread per pixel, 16-byte stores.
-__global__ __launch_bounds__(TPB) void k_image_u8_to_rows(const uint8_t* __restrict__ img, int B, int H, int W, const uint8_t* __restrict__ flip,
-                                                          int Cp, __bf16* __restrict__ rows) {
-  const int64_t n = (int64_t)B * H * W;
-  for (int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x; p < n; p += (int64_t)gridDim.x * TPB) {
-    const int w = (int)(p % W); const int64_t bh = p / W; const int b = (int)(bh / H);
-    const int ws = (flip && flip[b]) ? W - 1 - w : w;
-    const uint8_t* px = img + (bh * W + ws) * 3;
-    bf16x8 v;
-    for (int c = 0; c < 8; ++c) v[c] = (__bf16)0.0f;
-    for (int c = 0; c < 3; ++c) v[c] = f2bf(((float)px[c] / 255.0f - 0.5f) / 0.5f);
-    bf16x8* out = reinterpret_cast<bf16x8*>(rows + p * Cp);
-    out[0] = v;
-    bf16x8 z;
-    for (int c = 0; c < 8; ++c) z[c] = (__bf16)0.0f;
-    for (int g = 1; g < Cp / 8; ++g) out[g] = z;
-  }
-}
-// The VAE decoder's tail: fp32 rows [B*H*W][ld] (channels 0..2 of conv_out) -> uint8 RGB, every step a separately rounded fp32 op
-// (the library builds with -ffp-contract=off):
-//   mode 0 (torchvision make_grid(normalize=True, value_range=(lo, hi)) + save_image):
-//          v = (min(max(x, lo), hi) - lo) / (hi - lo);  u = trunc(min(max(v * 255 + 0.5, 0), 255))  (v * 255, then + 0.5)
-//   mode 1 (diffusers / SD generate-images.py):  v = min(max(x / 2 + 0.5, 0), 1);  u = rint(v * 255)  (half to even)
-//   mode 2 (DiT/sample_ddp.py:132):  u = trunc(min(max(127.5 * x + 128, 0), 255))  (the product, then the sum)
-// The rows hold samples b0 .. b0+B-1 of a batch of n.  nrow == 0: out = [n][H][W][3], this launch writes its B samples.  nrow > 0: out =
-// the make_grid canvas [Hc][Wc][3] (xmaps = min(nrow, n) columns, cells (H+p) x (W+p) behind a p-pixel border, n == 1: the bare image);
-// one thread per canvas pixel, each launch writes the pixels of its own samples and the launch with b0 == 0 also the pad pixels (byte 0).
-__device__ __forceinline__ uint8_t img_u8(float x, int mode, float lo, float hi) {
-  if (mode == 0) {
-    const float c = fminf(fmaxf(x, lo), hi);
-    const float v = (c - lo) / (hi - lo);
-    float t = v * 255.0f;
-    t = t + 0.5f;
-    t = fminf(fmaxf(t, 0.0f), 255.0f);
-    return (uint8_t)(int)t;
-  }
-  if (mode == SFRON_IMAGE_TRUNC) {
-    float t = 127.5f * x;
-    t = t + 128.0f;
-    t = fminf(fmaxf(t, 0.0f), 255.0f);
-    return (uint8_t)(int)t;
-  }
-  float v = x / 2.0f + 0.5f;
-  v = fminf(fmaxf(v, 0.0f), 1.0f);
-  return (uint8_t)(int)rintf(v * 255.0f);
-}
-__global__ __launch_bounds__(TPB) void k_rows_to_image_u8(const float* __restrict__ rows, int ld, int B, int H, int W, int mode, float lo,
-                                                          float hi, int xmaps, int pad, int Hc, int Wc, int b0, int n,
-                                                          uint8_t* __restrict__ out) {
-  const int64_t npx = (int64_t)Hc * Wc;
-  const int ch = H + pad, cw = W + pad;
-  for (int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x; q < npx; q += (int64_t)gridDim.x * TPB) {
-    int k, iy, ix;
-    if (xmaps == 0) {                                 // [n][H][W][3]: canvas = the B samples of this launch, one after the other
-      k = b0 + (int)(q / ((int64_t)H * W));
-      const int r = (int)(q % ((int64_t)H * W));
-      iy = r / W; ix = r - iy * W;
-    } else {
-      const int y = (int)(q / Wc) - pad, x = (int)(q % Wc) - pad;
-      bool img = y >= 0 && x >= 0;
-      k = -1; iy = ix = 0;
-      if (img) {
-        const int cy = y / ch, cx = x / cw;
-        iy = y - cy * ch; ix = x - cx * cw;
-        k = cy * xmaps + cx;
-        img = iy < H && ix < W && cx < xmaps && k < n;
-      }
-      if (!img) {
-        if (b0 == 0) { uint8_t* o = out + q * 3; o[0] = 0; o[1] = 0; o[2] = 0; }
-        continue;
-      }
-      if (k < b0 || k >= b0 + B) continue;
-    }
-    const float* px = rows + ((int64_t)(k - b0) * H * W + (int64_t)iy * W + ix) * ld;
-    const int64_t at = xmaps == 0 ? ((int64_t)k * H * W + (int64_t)iy * W + ix) * 3 : q * 3;
-    out[at + 0] = img_u8(px[0], mode, lo, hi);
-    out[at + 1] = img_u8(px[1], mode, lo, hi);
-    out[at + 2] = img_u8(px[2], mode, lo, hi);
-  }
-}
-__global__ __launch_bounds__(TPB) void k_rows_to_nchw(const float* __restrict__ rows, int ld, int B, int C, int HW, float* __restrict__ x) {
-  const int64_t n = (int64_t)B * C * HW;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int hw = (int)(i % HW); const int c = (int)((i / HW) % C); const int b = (int)(i / ((int64_t)HW * C));
-    x[i] = rows[((int64_t)b * HW + hw) * ld + c];
-  }
-}
-__global__ __launch_bounds__(TPB) void k_nchw_to_rows_f32(const float* __restrict__ x, int B, int C, int HW, int ld, float* __restrict__ rows) {
-  const int64_t n = (int64_t)B * HW * ld;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int c = (int)(i % ld); const int64_t p = i / ld; const int hw = (int)(p % HW); const int b = (int)(p / HW);
-    rows[i] = c < C ? x[((int64_t)b * C + c) * HW + hw] : 0.f;
-  }
-}
-
-// ---- GroupNorm(G groups, eps) (+ swish) (+ dropout mask) on NHWC rows, one workgroup per (sample, group)
-// y = bf16( act(xhat * gamma + beta) * (mask ? mask * drop_scale : 1) ), xhat = (x - mean) * rstd; saves mean / rstd
-__global__ __launch_bounds__(TPB) void k_gn_fwd(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                const float* __restrict__ beta, int HW, int C, int G, float eps, int swish,
-                                                const uint8_t* __restrict__ mask, float drop_scale, __bf16* __restrict__ y,
-                                                float* __restrict__ mean, float* __restrict__ rstd) {
-  __shared__ double red[2][TPB / 64];
-  __shared__ float stat[2];
-  const int b = blockIdx.x / G, gi = blockIdx.x % G, cg = C / G;
-  const float* xb = x + (size_t)b * HW * ldx + gi * cg;
-  const int n = HW * cg;
-  // thread (slot, c) = (tid / cg, tid % cg) walks the pixels slot, slot + tpc, ... of its channel (no per-element division)
-  const int tpc = TPB / cg, slot = threadIdx.x / cg, c = threadIdx.x - slot * cg;
-  double s = 0.0, ss = 0.0;
-  if (slot < tpc)
-    for (int p = slot; p < HW; p += tpc) {
-      const float v = xb[(size_t)p * ldx + c];
-      s += v; ss += (double)v * v;
-    }
-  s = wave_sum_d(s); ss = wave_sum_d(ss);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = ss; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0, q = 0;
-    for (int w = 0; w < TPB / 64; ++w) { a += red[0][w]; q += red[1][w]; }
-    const double m = a / n;
-    double var = q / n - m * m;                 // biased variance, as torch.nn.GroupNorm
-    var = var < 0 ? 0 : var;
-    stat[0] = (float)m; stat[1] = (float)(1.0 / sqrt(var + (double)eps));
-    mean[blockIdx.x] = stat[0]; rstd[blockIdx.x] = stat[1];
-  }
-  __syncthreads();
-  const float m = stat[0], r = stat[1];
-  __bf16* yb = y + (size_t)b * HW * C + gi * cg;
-  const uint8_t* mb = mask ? mask + (size_t)b * HW * C + gi * cg : nullptr;
-  if (slot < tpc) {
-    const float ga = gamma[gi * cg + c], be = beta[gi * cg + c];
-    for (int p = slot; p < HW; p += tpc) {
-      float z = (xb[(size_t)p * ldx + c] - m) * r * ga + be;
-      if (swish) z = silu(z);
-      if (mb) z = mb[(size_t)p * C + c] ? z * drop_scale : 0.f;
-      yb[(size_t)p * C + c] = f2bf(z);
-    }
-  }
-}
-// backward: dy = gradient wrt the bf16 output (fp32 rows, ld = C); dx (+)= d GroupNorm; per-sample partial parameter
-// gradients pg[b][C], pb[b][C] (summed over the batch by sfron_reduce_chunks: fixed order)
-__global__ __launch_bounds__(TPB) void k_gn_bwd(const float* __restrict__ dy, const float* __restrict__ x, int ldx,
-                                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                const float* __restrict__ mean, const float* __restrict__ rstd, int HW, int C, int G,
-                                                int swish, const uint8_t* __restrict__ mask, float drop_scale,
-                                                float* __restrict__ dx, int lddx, int accumulate, float* __restrict__ pg,
-                                                float* __restrict__ pb) {
-  extern __shared__ float sh[];                 // [TPB/64][2] wave partials + per-channel [2][cg] accumulators
-  const int b = blockIdx.x / G, gi = blockIdx.x % G, cg = C / G;
-  float* chs = sh + 2 * (TPB / 64);             // [2][cg]: sum dz * xhat, sum dz   per channel
-  const float m = mean[blockIdx.x], r = rstd[blockIdx.x];
-  const float* xb = x + (size_t)b * HW * ldx + gi * cg;
-  const float* dyb = dy + (size_t)b * HW * C + gi * cg;
-  const uint8_t* mb = mask ? mask + (size_t)b * HW * C + gi * cg : nullptr;
-  const int n = HW * cg;
-  // pass 1: dz = dy * act'(z) (* dropout); group sums of dz * gamma and dz * gamma * xhat; per-channel sums.
-  // Thread (slot, c) = (tid / cg, tid % cg) owns channel c and visits the pixels slot, slot + tpc, ... (tpc = TPB / cg slots; the
-  // TPB - tpc * cg surplus threads idle here): consecutive threads still read consecutive addresses of a pixel's cg-channel run, and
-  // every per-channel sum is formed in a fixed order (no atomics: bitwise reproducible for any channels-per-group <= TPB).
-  float s1 = 0.f, s2 = 0.f;
-  float ca = 0.f, cb = 0.f;
-  const int tpc = TPB / cg, slot = threadIdx.x / cg, c = threadIdx.x - slot * cg;
-  if (slot < tpc) {
-    const float ga = gamma[gi * cg + c], be = beta[gi * cg + c];
-    for (int p = slot; p < HW; p += tpc) {
-      const float xh = (xb[(size_t)p * ldx + c] - m) * r;
-      float d = dyb[(size_t)p * C + c];
-      if (mb) d = mb[(size_t)p * C + c] ? d * drop_scale : 0.f;
-      if (swish) d *= silu_grad(xh * ga + be);
-      s1 += d * ga; s2 += d * ga * xh;
-      ca += d * xh; cb += d;
-    }
-  }
-  float* tmp = sh + 2 * (TPB / 64) + 2 * cg;     // [2][TPB]
-  tmp[threadIdx.x] = ca; tmp[TPB + threadIdx.x] = cb;
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s1; sh[TPB / 64 + (threadIdx.x >> 6)] = s2; }
-  __syncthreads();
-  if (threadIdx.x < cg) {
-    float a = 0.f, q = 0.f;
-    for (int j = threadIdx.x; j < tpc * cg; j += cg) { a += tmp[j]; q += tmp[TPB + j]; }
-    chs[threadIdx.x] = a; chs[cg + threadIdx.x] = q;
-  }
-  float t1 = 0.f, t2 = 0.f;
-  for (int w = 0; w < TPB / 64; ++w) { t1 += sh[w]; t2 += sh[TPB / 64 + w]; }
-  __syncthreads();
-  if (threadIdx.x < cg) {
-    pg[(size_t)b * C + gi * cg + threadIdx.x] = chs[threadIdx.x];
-    pb[(size_t)b * C + gi * cg + threadIdx.x] = chs[cg + threadIdx.x];
-  }
-  const float inv = 1.0f / (float)n;
-  const float k1 = t1 * inv, k2 = t2 * inv;
-  float* dxb = dx + (size_t)b * HW * lddx + gi * cg;
-  if (slot < tpc) {
-    const float ga = gamma[gi * cg + c], be = beta[gi * cg + c];
-    for (int p = slot; p < HW; p += tpc) {
-      const float xh = (xb[(size_t)p * ldx + c] - m) * r;
-      float d = dyb[(size_t)p * C + c];
-      if (mb) d = mb[(size_t)p * C + c] ? d * drop_scale : 0.f;
-      if (swish) d *= silu_grad(xh * ga + be);
-      const float v = r * (d * ga - k1 - xh * k2);
-      float* o = dxb + (size_t)p * lddx + c;
-      *o = accumulate ? *o + v : v;
-    }
-  }
-}
-
-// ---- GroupNorm, row-coalesced two-phase form (the production path; the per-(sample, group) kernels above serve odd shapes).
-// NHWC rows: a (sample, group) slab is HW runs of cg floats, 4 * C bytes apart -- a workgroup per slab touches 16..40 useful bytes of
-// every 128-B line.  Here a workgroup owns a CHUNK OF PIXELS of one sample and all C channels: threads read whole rows as float4
-// (thread = (row replica r, quad lane q); C / 4 quads per row, up to three quads per thread for C > 1024), so every load is a
-// full-line stream.  Phase 1 leaves per-chunk partial sums, phase 2 (same chunking) combines them in a fixed order in its
-// prologue and applies the normalisation; all per-channel / per-group sums are formed in a fixed order (bitwise reproducible).
-constexpr int GNB = 1024;                       // 16 waves per workgroup: with one workgroup per (sample, chunk) the chip is only full this way
-constexpr int GN_MAXQ = 1;                      // quads per thread: C <= 4 * GNB = 4096
-struct GnMap {
-  int qpr, qw, rpp, r, ql, nq;                  // quads per row, quad lanes, rows per pass, this thread's row replica / lane, its quads
-  __device__ __forceinline__ void init(int C) {
-    qpr = C >> 2; qw = qpr < GNB ? qpr : GNB; rpp = GNB / qw;
-    r = threadIdx.x / qw; ql = threadIdx.x - r * qw; nq = (qpr - ql + qw - 1) / qw;
-    if (r >= rpp) nq = 0;
-  }
-};
-__host__ __device__ inline int gn_chunks(int B, int HW) {
-  int n = (512 + B - 1) / B;
-  if (n > 32) n = 32;
-  if (n > HW / 8) n = HW / 8;
-  return n < 1 ? 1 : n;
-}
-
-// phase 1 forward: partial (sum, sum of squares) per (sample, chunk, group), fp64
-__global__ __launch_bounds__(GNB) void k_gn2_stats(const float* __restrict__ x, int ldx, int HW, int C, int G, int nchunk, double* __restrict__ part) {
-  extern __shared__ double shd[];               // [rpp][C][2]
-  const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk, cg = C / G;
-  const int p0 = (int)((long)HW * ch / nchunk), p1 = (int)((long)HW * (ch + 1) / nchunk);
-  GnMap m; m.init(C);
-  double s[GN_MAXQ][4], ss[GN_MAXQ][4];
-#pragma unroll
-  for (int j = 0; j < GN_MAXQ; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { s[j][e] = 0.0; ss[j][e] = 0.0; }
-  const float* xb = x + (size_t)b * HW * ldx;
-  for (int p = p0 + m.r; p < p1; p += m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq) {
-        const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx + 4 * (m.ql + j * m.qw));
-        s[j][0] += v.x; ss[j][0] += (double)v.x * v.x; s[j][1] += v.y; ss[j][1] += (double)v.y * v.y;
-        s[j][2] += v.z; ss[j][2] += (double)v.z * v.z; s[j][3] += v.w; ss[j][3] += (double)v.w * v.w;
-      }
-  }
-  if (m.r < m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * (m.ql + j * m.qw) + e;
-          shd[((size_t)m.r * C + c) * 2] = s[j][e]; shd[((size_t)m.r * C + c) * 2 + 1] = ss[j][e];
-        }
-  }
-  __syncthreads();
-  // one wave per group at a time: lane l adds the words l, l + 64, ... of the group's [rpp][cg] block in index order, then a butterfly
-  // over the lanes -- a fixed order (bitwise reproducible).  (Was: G threads walking rpp * cg words each, 256 dependent LDS reads
-  // = most of the kernel at the small levels.)
-  const int lane = threadIdx.x & 63, nw = GNB / 64, per = m.rpp * cg;
-  for (int g = threadIdx.x >> 6; g < G; g += nw) {
-    double a = 0.0, q = 0.0;
-    for (int i = lane; i < per; i += 64) {
-      const int r = i / cg, c = g * cg + (i - r * cg);
-      a += shd[((size_t)r * C + c) * 2]; q += shd[((size_t)r * C + c) * 2 + 1];
-    }
-    a = wave_sum_d(a); q = wave_sum_d(q);
-    if (lane == 0) { double* o = part + (((size_t)b * nchunk + ch) * G + g) * 2; o[0] = a; o[1] = q; }
-  }
-}
-// phase 2 forward: mean / rstd from the partials (every workgroup of a sample forms them the same way; chunk 0 stores them), apply
-__global__ __launch_bounds__(GNB) void k_gn2_apply(const float* __restrict__ x, int ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                   int HW, int C, int G, float eps, int swish, const uint8_t* __restrict__ mask, float drop_scale,
-                                                   int nchunk, const double* __restrict__ part, __bf16* __restrict__ y, float* __restrict__ mean,
-                                                   float* __restrict__ rstd) {
-  __shared__ float st[2][64];
-  __shared__ double sp[32 * 64 * 2];            // [chunk][group][2]: every partial of the sample, fetched by nchunk * G threads at once
-  const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk, cg = C / G;
-  for (int i = threadIdx.x; i < nchunk * G * 2; i += GNB) sp[i] = part[(size_t)b * nchunk * G * 2 + i];
-  __syncthreads();
-  if (threadIdx.x < G) {
-    double a = 0.0, q = 0.0;
-    for (int k = 0; k < nchunk; ++k) { const double* o = sp + ((size_t)k * G + threadIdx.x) * 2; a += o[0]; q += o[1]; }
-    const double n = (double)HW * cg, mu = a / n;
-    double var = q / n - mu * mu;                 // biased variance, as torch.nn.GroupNorm
-    var = var < 0 ? 0 : var;
-    st[0][threadIdx.x] = (float)mu; st[1][threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
-    if (ch == 0) { mean[b * G + threadIdx.x] = st[0][threadIdx.x]; rstd[b * G + threadIdx.x] = st[1][threadIdx.x]; }
-  }
-  __syncthreads();
-  const int p0 = (int)((long)HW * ch / nchunk), p1 = (int)((long)HW * (ch + 1) / nchunk);
-  GnMap m; m.init(C);
-  float mu[GN_MAXQ][4], rs[GN_MAXQ][4], ga[GN_MAXQ][4], be[GN_MAXQ][4];
-#pragma unroll
-  for (int j = 0; j < GN_MAXQ; ++j)
-    if (j < m.nq)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = 4 * (m.ql + j * m.qw) + e, gi = c / cg;
-        mu[j][e] = st[0][gi]; rs[j][e] = st[1][gi]; ga[j][e] = gamma[c]; be[j][e] = beta[c];
-      }
-  const float* xb = x + (size_t)b * HW * ldx;
-  __bf16* yb = y + (size_t)b * HW * C;
-  const uint8_t* mb = mask ? mask + (size_t)b * HW * C : nullptr;
-  for (int p = p0 + m.r; p < p1; p += m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq) {
-        const int c0 = 4 * (m.ql + j * m.qw);
-        const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx + c0);
-        float z[4] = {v.x, v.y, v.z, v.w};
-        uchar4 mk = make_uchar4(1, 1, 1, 1);
-        if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C + c0);
-        const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float t = (z[e] - mu[j][e]) * rs[j][e] * ga[j][e] + be[j][e];
-          if (swish) t = silu(t);
-          if (mb) t = mke[e] ? t * drop_scale : 0.f;
-          z[e] = t;
-        }
-        *reinterpret_cast<bf16x4*>(yb + (size_t)p * C + c0) = bf16x4{f2bf(z[0]), f2bf(z[1]), f2bf(z[2]), f2bf(z[3])};
-      }
-  }
-}
-// phase 1 backward: per (sample, chunk, channel) partial sums of dz * xhat and dz, dz = dy * act'(z) (* dropout)
-__global__ __launch_bounds__(GNB) void k_gn2_bwd_stats(const float* __restrict__ dy, const float* __restrict__ x, int ldx,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       const float* __restrict__ mean, const float* __restrict__ rstd, int HW, int C, int G,
-                                                       int swish, const uint8_t* __restrict__ mask, float drop_scale, int nchunk,
-                                                       float* __restrict__ part) {
-  extern __shared__ float shf[];                // [rpp][C][2]
-  const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk, cg = C / G;
-  const int p0 = (int)((long)HW * ch / nchunk), p1 = (int)((long)HW * (ch + 1) / nchunk);
-  GnMap m; m.init(C);
-  float mu[GN_MAXQ][4], rs[GN_MAXQ][4], ga[GN_MAXQ][4], be[GN_MAXQ][4], ca[GN_MAXQ][4], cb[GN_MAXQ][4];
-#pragma unroll
-  for (int j = 0; j < GN_MAXQ; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      ca[j][e] = 0.f; cb[j][e] = 0.f;
-      if (j < m.nq) {
-        const int c = 4 * (m.ql + j * m.qw) + e, gi = c / cg;
-        mu[j][e] = mean[b * G + gi]; rs[j][e] = rstd[b * G + gi]; ga[j][e] = gamma[c]; be[j][e] = beta[c];
-      }
-    }
-  const float* xb = x + (size_t)b * HW * ldx;
-  const float* dyb = dy + (size_t)b * HW * C;
-  const uint8_t* mb = mask ? mask + (size_t)b * HW * C : nullptr;
-  for (int p = p0 + m.r; p < p1; p += m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq) {
-        const int c0 = 4 * (m.ql + j * m.qw);
-        const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx + c0);
-        const float4 dv = *reinterpret_cast<const float4*>(dyb + (size_t)p * C + c0);
-        uchar4 mk = make_uchar4(1, 1, 1, 1);
-        if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C + c0);
-        const float xv[4] = {v.x, v.y, v.z, v.w}, dd[4] = {dv.x, dv.y, dv.z, dv.w};
-        const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xh = (xv[e] - mu[j][e]) * rs[j][e];
-          float d = dd[e];
-          if (mb) d = mke[e] ? d * drop_scale : 0.f;
-          if (swish) d *= silu_grad(xh * ga[j][e] + be[j][e]);
-          ca[j][e] += d * xh; cb[j][e] += d;
-        }
-      }
-  }
-  if (m.r < m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * (m.ql + j * m.qw) + e;
-          shf[((size_t)m.r * C + c) * 2] = ca[j][e]; shf[((size_t)m.r * C + c) * 2 + 1] = cb[j][e];
-        }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += GNB) {
-    float a = 0.f, q = 0.f;
-    for (int r = 0; r < m.rpp; ++r) { a += shf[((size_t)r * C + c) * 2]; q += shf[((size_t)r * C + c) * 2 + 1]; }
-    float* o = part + (((size_t)b * nchunk + ch) * C + c) * 2;
-    o[0] = a; o[1] = q;
-  }
-}
-// phase 2 backward: per-channel sums over the chunks -> (chunk 0) the per-sample parameter-gradient partials, the group means
-// k1 = mean(dz gamma), k2 = mean(dz gamma xhat); dx (+)= rstd (dz gamma - k1 - xhat k2)
-__global__ __launch_bounds__(GNB) void k_gn2_bwd_apply(const float* __restrict__ dy, const float* __restrict__ x, int ldx,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       const float* __restrict__ mean, const float* __restrict__ rstd, int HW, int C, int G,
-                                                       int swish, const uint8_t* __restrict__ mask, float drop_scale, int nchunk,
-                                                       const float* __restrict__ part, float* __restrict__ dx, int lddx, int accumulate,
-                                                       float* __restrict__ pg, float* __restrict__ pb, const float* __restrict__ extra,
-                                                       int ldextra, __bf16* __restrict__ dx16, float* __restrict__ colpart) {
-  // dx16 / colpart (sfron_groupnorm_bwd_cast): the gradient also (or only: dx == nullptr) as the bf16 GEMM operand [rows][C] of the
-  // convolution that produced x, and its column sums per (sample, chunk) -- that layer's bias gradient and, per sample, the gradient
-  // of a per-sample vector added to x -- which a cast pass and two column-sum passes over an fp32 dx would form otherwise
-  extern __shared__ float shf[];                // [C][2] channel sums, then [G][2] group means
-  const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk, cg = C / G;
-  float* kk = shf + 2 * C;
-  float* sg = kk + 2 * G;                       // gamma, staged for the group sums below
-  for (int c = threadIdx.x; c < C; c += GNB) {
-    float a = 0.f, q = 0.f;
-    sg[c] = gamma[c];
-    for (int k0 = 0; k0 < nchunk; k0 += 8) {    // eight partial pairs in flight (a load-use loop pays one L2 latency per chunk)
-      float2 t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int k = k0 + u < nchunk ? k0 + u : nchunk - 1;
-        t[u] = *reinterpret_cast<const float2*>(part + (((size_t)b * nchunk + k) * C + c) * 2);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (k0 + u < nchunk) { a += t[u].x; q += t[u].y; }
-    }
-    shf[2 * c] = a; shf[2 * c + 1] = q;
-    if (ch == 0) { pg[(size_t)b * C + c] = a; pb[(size_t)b * C + c] = q; }
-  }
-  __syncthreads();
-  if (threadIdx.x < G) {
-    float t1 = 0.f, t2 = 0.f;
-    for (int c = threadIdx.x * cg; c < (threadIdx.x + 1) * cg; ++c) { const float g1 = sg[c]; t1 += g1 * shf[2 * c + 1]; t2 += g1 * shf[2 * c]; }
-    const float inv = 1.0f / ((float)HW * (float)cg);
-    kk[2 * threadIdx.x] = t1 * inv; kk[2 * threadIdx.x + 1] = t2 * inv;
-  }
-  __syncthreads();
-  const int p0 = (int)((long)HW * ch / nchunk), p1 = (int)((long)HW * (ch + 1) / nchunk);
-  GnMap m; m.init(C);
-  float mu[GN_MAXQ][4], rs[GN_MAXQ][4], ga[GN_MAXQ][4], be[GN_MAXQ][4], k1[GN_MAXQ][4], k2[GN_MAXQ][4];
-#pragma unroll
-  for (int j = 0; j < GN_MAXQ; ++j)
-    if (j < m.nq)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = 4 * (m.ql + j * m.qw) + e, gi = c / cg;
-        mu[j][e] = mean[b * G + gi]; rs[j][e] = rstd[b * G + gi]; ga[j][e] = gamma[c]; be[j][e] = beta[c];
-        k1[j][e] = kk[2 * gi]; k2[j][e] = kk[2 * gi + 1];
-      }
-  const float* xb = x + (size_t)b * HW * ldx;
-  const float* dyb = dy + (size_t)b * HW * C;
-  const uint8_t* mb = mask ? mask + (size_t)b * HW * C : nullptr;
-  float* dxb = dx ? dx + (size_t)b * HW * lddx : nullptr;
-  __bf16* d16b = dx16 ? dx16 + (size_t)b * HW * C : nullptr;
-  const float* exb = extra ? extra + (size_t)b * HW * ldextra : nullptr;
-  float cs[GN_MAXQ][4];
-#pragma unroll
-  for (int j = 0; j < GN_MAXQ; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) cs[j][e] = 0.f;
-  for (int p = p0 + m.r; p < p1; p += m.rpp) {
-#pragma unroll
-    for (int j = 0; j < GN_MAXQ; ++j)
-      if (j < m.nq) {
-        const int c0 = 4 * (m.ql + j * m.qw);
-        const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx + c0);
-        const float4 dv = *reinterpret_cast<const float4*>(dyb + (size_t)p * C + c0);
-        uchar4 mk = make_uchar4(1, 1, 1, 1);
-        if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C + c0);
-        const float xv[4] = {v.x, v.y, v.z, v.w}, dd[4] = {dv.x, dv.y, dv.z, dv.w};
-        const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-        float4* op = dxb ? reinterpret_cast<float4*>(dxb + (size_t)p * lddx + c0) : nullptr;
-        float o[4] = {0.f, 0.f, 0.f, 0.f};
-        if (accumulate) { const float4 c = *op; o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w; }
-        if (exb) {             // the term a separate dx (+)= extra pass would have added first: (dx + extra) + this layer's gradient
-          const float4 c = *reinterpret_cast<const float4*>(exb + (size_t)p * ldextra + c0);
-          o[0] += c.x; o[1] += c.y; o[2] += c.z; o[3] += c.w;
-        }
-        const bool acc = accumulate || exb;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xh = (xv[e] - mu[j][e]) * rs[j][e];
-          float d = dd[e];
-          if (mb) d = mke[e] ? d * drop_scale : 0.f;
-          if (swish) d *= silu_grad(xh * ga[j][e] + be[j][e]);
-          const float vv = rs[j][e] * (d * ga[j][e] - k1[j][e] - xh * k2[j][e]);
-          o[e] = acc ? o[e] + vv : vv;
-        }
-        if (op) *op = make_float4(o[0], o[1], o[2], o[3]);
-        if (d16b) *reinterpret_cast<bf16x4*>(d16b + (size_t)p * C + c0) = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
-        if (colpart) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) cs[j][e] += o[e];
-        }
-      }
-  }
-  if (colpart) {                                // the row replicas' column sums meet in LDS in replica order (fixed order)
-    float* red = shf + 3 * C + 2 * G;           // [rpp][C]
-    if (m.r < m.rpp) {
-#pragma unroll
-      for (int j = 0; j < GN_MAXQ; ++j)
-        if (j < m.nq)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) red[(size_t)m.r * C + 4 * (m.ql + j * m.qw) + e] = cs[j][e];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += GNB) {
-      float a = 0.f;
-      for (int r = 0; r < m.rpp; ++r) a += red[(size_t)r * C + c];
-      colpart[((size_t)b * nchunk + ch) * C + c] = a;
-    }
-  }
-}
-
-// ---- GroupNorm in ONE launch per direction (round 6): a workgroup owns one sample and a block of `gpb` whole groups = Cs = gpb * C / G
-// consecutive channels over ALL pixels -- statistics and normalisation never leave the workgroup, so the two phases of the k_gn2 pair (and the
-// ~5 us boundary between two dependent launches, which at the 16 x 16 ... 4 x 4 levels of the DDPM U-Net is as long as either phase) become
-// two passes of one kernel over a slab of at most 128 KB that the second pass finds in L2.  B * G / gpb workgroups (DDPM batch 64: 256 .. 1024):
-// the chip stays full, which one workgroup per sample (round 5, profiles/r05_ab_log.txt) did not manage.  Rows are runs of Cs floats
-// (>= 64 bytes), read as float4 by (row replica r, quad q) threads.  The same arithmetic per element as k_gn2_*; the sums run over this
-// workgroup's rows in a fixed order (replica r takes rows r, r + rpp, ...; replicas, then channels, are added in index order): bitwise
-// reproducible, not bit-identical to the chunked pair.
-constexpr int GN3_T = 1024;
-// the GroupNorm INPUT (forward: x, backward: dy) as the still unfinished result of a split-K product (round 6): n slabs [rows][C] to be added in
-// index order, + bias[c] + vec[sample][c] + resid[row][c] -- element for element what k_split_finish4 writes.  The one-launch kernels form each
-// element in their first pass, store it to the tensor the finish launch would have filled (their own second pass and every later reader find
-// it there), and the finish launch between the product and the GroupNorm no longer exists.  slabs == nullptr: the input is a finished tensor.
-struct Gn3Src {
-  const float* slabs; int n; int64_t stride;
-  const float* bias; const float* vec; int ldvec; const float* resid; int ldresid;
-};
-__device__ __forceinline__ float4 gn3_src_quad(const Gn3Src& s, int64_t row, int b, int c, int C) {
-  const float* p = s.slabs + row * C + c;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  int sl = 0;
-  for (; sl + 4 <= s.n; sl += 4) {                // four slab loads in flight, added in slab order
-    float4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(p + (sl + u) * s.stride);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
-  }
-  for (; sl < s.n; ++sl) { const float4 v = *reinterpret_cast<const float4*>(p + sl * s.stride); a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-  float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (s.bias) b4 = *reinterpret_cast<const float4*>(s.bias + c);
-  a.x += b4.x; a.y += b4.y; a.z += b4.z; a.w += b4.w;
-  if (s.vec) { const float4 v = *reinterpret_cast<const float4*>(s.vec + (int64_t)b * s.ldvec + c); a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-  if (s.resid) { const float4 v = *reinterpret_cast<const float4*>(s.resid + row * s.ldresid + c); a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-  return a;
-}
-struct Gn3Map {
-  int b, g0, c0, Cs, qpr, rpp, q, r;
-  bool on;
-  __device__ __forceinline__ void init(int C, int G, int gpb) {
-    const int ncb = G / gpb, cg = C / G;
-    b = blockIdx.x / ncb;
-    g0 = (blockIdx.x - b * ncb) * gpb; c0 = g0 * cg; Cs = gpb * cg; qpr = Cs >> 2; rpp = GN3_T / qpr;
-    r = threadIdx.x / qpr; q = threadIdx.x - r * qpr; on = r < rpp;
-  }
-};
-template <bool SRC>
-__global__ __launch_bounds__(GN3_T) void k_gn3_fwd(const float* __restrict__ x, int ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                   int HW, int C, int G, int gpb, float eps, int swish, const uint8_t* __restrict__ mask,
-                                                   float drop_scale, __bf16* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
-                                                   Gn3Src src) {
-  __shared__ double shd[GN3_T * 4 * 2];         // [rpp][Cs][2], rpp * Cs <= 4 * GN3_T
-  __shared__ float st[2][64];
-  Gn3Map m; m.init(C, G, gpb);
-  const int cg = C / G;
-  const float* xb = x + (size_t)m.b * HW * ldx + m.c0 + 4 * m.q;
-  double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-  if (SRC && m.on) {                              // x is still S slabs: finish it here (ldx == C), this thread's quads, for its own second pass
-    float* xw = const_cast<float*>(xb);
-#pragma unroll 2
-    for (int p = m.r; p < HW; p += m.rpp) {
-      const float4 v = gn3_src_quad(src, (int64_t)m.b * HW + p, m.b, m.c0 + 4 * m.q, C);
-      *reinterpret_cast<float4*>(xw + (size_t)p * ldx) = v;
-      s[0] += v.x; ss[0] += (double)v.x * v.x; s[1] += v.y; ss[1] += (double)v.y * v.y;
-      s[2] += v.z; ss[2] += (double)v.z * v.z; s[3] += v.w; ss[3] += (double)v.w * v.w;
-    }
-  } else if (!SRC && m.on) {
-#pragma unroll 8
-    for (int p = m.r; p < HW; p += m.rpp) {
-      const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx);
-      s[0] += v.x; ss[0] += (double)v.x * v.x; s[1] += v.y; ss[1] += (double)v.y * v.y;
-      s[2] += v.z; ss[2] += (double)v.z * v.z; s[3] += v.w; ss[3] += (double)v.w * v.w;
-    }
-  }
-  if (m.on) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      shd[((size_t)m.r * m.Cs + 4 * m.q + e) * 2] = s[e]; shd[((size_t)m.r * m.Cs + 4 * m.q + e) * 2 + 1] = ss[e];
-    }
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, per = m.rpp * cg;
-  for (int g = threadIdx.x >> 6; g < gpb; g += GN3_T / 64) {      // one wave per group at a time, as k_gn2_stats
-    double a = 0.0, q = 0.0;
-    for (int i = lane; i < per; i += 64) {
-      const int r = i / cg, c = g * cg + (i - r * cg);
-      a += shd[((size_t)r * m.Cs + c) * 2]; q += shd[((size_t)r * m.Cs + c) * 2 + 1];
-    }
-    a = wave_sum_d(a); q = wave_sum_d(q);
-    if (lane == 0) {
-      const double n = (double)HW * cg, mu = a / n;
-      double var = q / n - mu * mu;                 // biased variance, as torch.nn.GroupNorm
-      var = var < 0 ? 0 : var;
-      st[0][g] = (float)mu; st[1][g] = (float)(1.0 / sqrt(var + (double)eps));
-      mean[m.b * G + m.g0 + g] = st[0][g]; rstd[m.b * G + m.g0 + g] = st[1][g];
-    }
-  }
-  __syncthreads();
-  if (!m.on) return;
-  float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int c = 4 * m.q + e, gi = c / cg;
-    mu[e] = st[0][gi]; rs[e] = st[1][gi]; ga[e] = gamma[m.c0 + c]; be[e] = beta[m.c0 + c];
-  }
-  __bf16* yb = y + (size_t)m.b * HW * C + m.c0 + 4 * m.q;
-  const uint8_t* mb = mask ? mask + (size_t)m.b * HW * C + m.c0 + 4 * m.q : nullptr;
-#pragma unroll 8
-  for (int p = m.r; p < HW; p += m.rpp) {
-    const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx);
-    float z[4] = {v.x, v.y, v.z, v.w};
-    uchar4 mk = make_uchar4(1, 1, 1, 1);
-    if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C);
-    const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float t = (z[e] - mu[e]) * rs[e] * ga[e] + be[e];
-      if (swish) t = silu(t);
-      if (mb) t = mke[e] ? t * drop_scale : 0.f;
-      z[e] = t;
-    }
-    *reinterpret_cast<bf16x4*>(yb + (size_t)p * C) = bf16x4{f2bf(z[0]), f2bf(z[1]), f2bf(z[2]), f2bf(z[3])};
-  }
-}
-// backward of the same decomposition: pass 1 = per-channel sums of dz xhat and dz over the sample (the parameter-gradient partials pg / pb of
-// this sample, complete here) -> the group means k1, k2; pass 2 = dx (+)= rstd (dz gamma - k1 - xhat k2), every output form of k_gn2_bwd_apply
-// (fp32 with accumulate / extra, bf16 operand copy, per-sample column sums: colpart keeps the caller's [B][nchunk][C] layout -- chunk 0 gets the
-// sample's sum, the other chunks zeros)
-template <bool SRC>
-__global__ __launch_bounds__(GN3_T) void k_gn3_bwd(const float* __restrict__ dy, const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                   const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                   int HW, int C, int G, int gpb, int swish, const uint8_t* __restrict__ mask, float drop_scale,
-                                                   float* __restrict__ dx, int lddx, int accumulate, float* __restrict__ pg, float* __restrict__ pb,
-                                                   const float* __restrict__ extra, int ldextra, __bf16* __restrict__ dx16,
-                                                   float* __restrict__ colpart, int nchunk, Gn3Src src) {
-  __shared__ float shf[GN3_T * 4 * 2];          // [rpp][Cs][2]; afterwards [rpp][Cs] column sums
-  __shared__ float chs[GN3_T * 4 * 2 / (GN3_T / 256)];          // [Cs][2] channel sums, Cs <= 1024
-  __shared__ float kk[2 * 64];
-  Gn3Map m; m.init(C, G, gpb);
-  const int cg = C / G;
-  float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int c = 4 * m.q + e, gi = m.g0 + c / cg;
-    mu[e] = 0.f; rs[e] = 0.f; ga[e] = 0.f; be[e] = 0.f;
-    if (m.on) { mu[e] = mean[m.b * G + gi]; rs[e] = rstd[m.b * G + gi]; ga[e] = gamma[m.c0 + c]; be[e] = beta[m.c0 + c]; }
-  }
-  const float* xb = x + (size_t)m.b * HW * ldx + m.c0 + 4 * m.q;
-  const float* dyb = dy + (size_t)m.b * HW * C + m.c0 + 4 * m.q;
-  const uint8_t* mb = mask ? mask + (size_t)m.b * HW * C + m.c0 + 4 * m.q : nullptr;
-  if (m.on) {
-    float ca[4] = {0.f, 0.f, 0.f, 0.f}, cb[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll SRC ? 2 : 8
-    for (int p = m.r; p < HW; p += m.rpp) {
-      const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx);
-      float4 dv;
-      if constexpr (SRC) {                          // dy is still S slabs (an input-gradient convolution): finished here, stored for pass 2
-        dv = gn3_src_quad(src, (int64_t)m.b * HW + p, m.b, m.c0 + 4 * m.q, C);
-        *reinterpret_cast<float4*>(const_cast<float*>(dyb) + (size_t)p * C) = dv;
-      } else
-        dv = *reinterpret_cast<const float4*>(dyb + (size_t)p * C);
-      uchar4 mk = make_uchar4(1, 1, 1, 1);
-      if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C);
-      const float xv[4] = {v.x, v.y, v.z, v.w}, dd[4] = {dv.x, dv.y, dv.z, dv.w};
-      const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float xh = (xv[e] - mu[e]) * rs[e];
-        float d = dd[e];
-        if (mb) d = mke[e] ? d * drop_scale : 0.f;
-        if (swish) d *= silu_grad(xh * ga[e] + be[e]);
-        ca[e] += d * xh; cb[e] += d;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      shf[((size_t)m.r * m.Cs + 4 * m.q + e) * 2] = ca[e]; shf[((size_t)m.r * m.Cs + 4 * m.q + e) * 2 + 1] = cb[e];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < m.Cs; c += GN3_T) {
-    float a = 0.f, q = 0.f;
-    for (int r = 0; r < m.rpp; ++r) { a += shf[((size_t)r * m.Cs + c) * 2]; q += shf[((size_t)r * m.Cs + c) * 2 + 1]; }
-    chs[2 * c] = a; chs[2 * c + 1] = q;
-    pg[(size_t)m.b * C + m.c0 + c] = a; pb[(size_t)m.b * C + m.c0 + c] = q;
-  }
-  __syncthreads();
-  if (threadIdx.x < gpb) {
-    float t1 = 0.f, t2 = 0.f;
-    for (int c = threadIdx.x * cg; c < (threadIdx.x + 1) * cg; ++c) { const float g1 = gamma[m.c0 + c]; t1 += g1 * chs[2 * c + 1]; t2 += g1 * chs[2 * c]; }
-    const float inv = 1.0f / ((float)HW * (float)cg);
-    kk[2 * threadIdx.x] = t1 * inv; kk[2 * threadIdx.x + 1] = t2 * inv;
-  }
-  __syncthreads();
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  if (m.on) {
-    float k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const int gi = (4 * m.q + e) / cg; k1[e] = kk[2 * gi]; k2[e] = kk[2 * gi + 1]; }
-    float* dxb = dx ? dx + (size_t)m.b * HW * lddx + m.c0 + 4 * m.q : nullptr;
-    __bf16* d16b = dx16 ? dx16 + (size_t)m.b * HW * C + m.c0 + 4 * m.q : nullptr;
-    const float* exb = extra ? extra + (size_t)m.b * HW * ldextra + m.c0 + 4 * m.q : nullptr;
-#pragma unroll 4
-    for (int p = m.r; p < HW; p += m.rpp) {
-      const float4 v = *reinterpret_cast<const float4*>(xb + (size_t)p * ldx);
-      const float4 dv = *reinterpret_cast<const float4*>(dyb + (size_t)p * C);
-      uchar4 mk = make_uchar4(1, 1, 1, 1);
-      if (mb) mk = *reinterpret_cast<const uchar4*>(mb + (size_t)p * C);
-      const float xv[4] = {v.x, v.y, v.z, v.w}, dd[4] = {dv.x, dv.y, dv.z, dv.w};
-      const uint8_t mke[4] = {mk.x, mk.y, mk.z, mk.w};
-      float4* op = dxb ? reinterpret_cast<float4*>(dxb + (size_t)p * lddx) : nullptr;
-      float o[4] = {0.f, 0.f, 0.f, 0.f};
-      if (accumulate) { const float4 c = *op; o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w; }
-      if (exb) {
-        const float4 c = *reinterpret_cast<const float4*>(exb + (size_t)p * ldextra);
-        o[0] += c.x; o[1] += c.y; o[2] += c.z; o[3] += c.w;
-      }
-      const bool acc = accumulate || exb;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float xh = (xv[e] - mu[e]) * rs[e];
-        float d = dd[e];
-        if (mb) d = mke[e] ? d * drop_scale : 0.f;
-        if (swish) d *= silu_grad(xh * ga[e] + be[e]);
-        const float vv = rs[e] * (d * ga[e] - k1[e] - xh * k2[e]);
-        o[e] = acc ? o[e] + vv : vv;
-      }
-      if (op) *op = make_float4(o[0], o[1], o[2], o[3]);
-      if (d16b) *reinterpret_cast<bf16x4*>(d16b + (size_t)p * C) = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
-      if (colpart) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) cs[e] += o[e];
-      }
-    }
-  }
-  if (colpart) {
-    __syncthreads();                            // every reader of shf's channel partials is done
-    if (m.on) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) shf[(size_t)m.r * m.Cs + 4 * m.q + e] = cs[e];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < m.Cs; c += GN3_T) {
-      float a = 0.f;
-      for (int r = 0; r < m.rpp; ++r) a += shf[(size_t)r * m.Cs + c];
-      colpart[((size_t)m.b * nchunk) * C + m.c0 + c] = a;
-      for (int k = 1; k < nchunk; ++k) colpart[((size_t)m.b * nchunk + k) * C + m.c0 + c] = 0.f;
-    }
-  }
-}
-
-// ---- softmax over rows of length n (fp32 in, bf16 out), one wave per row; backward dS = scale * P * (dP - sum(P dP))
-// rows of `n` stored elements of which the first `nv` are keys (the rest is padding of the context length: probability 0)
-__global__ __launch_bounds__(TPB) void k_softmax_fwd(const float* __restrict__ s, int64_t rows, int n, int nv, float scale, __bf16* __restrict__ p) {
-  const int64_t row = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const float* sr = s + row * n;
-  float mx = -INFINITY;
-  for (int i = lane; i < nv; i += 64) mx = fmaxf(mx, sr[i] * scale);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int i = lane; i < nv; i += 64) sum += __expf(sr[i] * scale - mx);
-  sum = wave_sum(sum);
-  const float inv = 1.0f / sum;
-  for (int i = lane; i < n; i += 64) p[row * n + i] = i < nv ? f2bf(__expf(sr[i] * scale - mx) * inv) : (__bf16)0.0f;
-}
-__global__ __launch_bounds__(TPB) void k_softmax_bwd(const __bf16* __restrict__ p, const float* __restrict__ dp, int64_t rows, int n,
-                                                     float scale, __bf16* __restrict__ ds) {
-  const int64_t row = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  float dot = 0.f;
-  for (int i = lane; i < n; i += 64) dot += bf2f(p[row * n + i]) * dp[row * n + i];
-  dot = wave_sum(dot);
-  for (int i = lane; i < n; i += 64) ds[row * n + i] = f2bf(scale * bf2f(p[row * n + i]) * (dp[row * n + i] - dot));
-}
-
-// ---- LayerNorm(D, eps, affine) on rows, one wave per row (BasicTransformerBlock.norm1..3, SD/ldm/modules/attention.py:223-225)
-__global__ __launch_bounds__(TPB) void k_layernorm_fwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int64_t rows, int D, float eps, __bf16* __restrict__ y, float* __restrict__ mean,
-                                                       float* __restrict__ rstd) {
-  const int64_t row = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const float* xr = x + row * D;
-  float s = 0.f;
-  for (int i = lane; i < D; i += 64) s += xr[i];
-  const float m = wave_sum(s) / D;
-  float q = 0.f;
-  for (int i = lane; i < D; i += 64) { const float d = xr[i] - m; q += d * d; }
-  const float r = rsqrtf(wave_sum(q) / D + eps);
-  for (int i = lane; i < D; i += 64) y[row * D + i] = f2bf((xr[i] - m) * r * gamma[i] + beta[i]);
-  if (lane == 0) { mean[row] = m; rstd[row] = r; }
-}
-// the same with the row in registers as float4 chunks (one 16-byte load per chunk, D <= 256 * NC, D % 4 == 0)
-template <int NC>
-__global__ __launch_bounds__(TPB) void k_layernorm_fwd_r(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         int64_t rows, int D, float eps, __bf16* __restrict__ y, float* __restrict__ mean,
-                                                         float* __restrict__ rstd) {
-  const int64_t row = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63, D4 = D >> 2;
-  const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-  float4 v[NC];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const int c = lane + 64 * j;
-    v[j] = c < D4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-  }
-  const float m = wave_sum(s) / D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < NC; ++j)
-    if (lane + 64 * j < D4) {
-      const float a = v[j].x - m, b = v[j].y - m, c2 = v[j].z - m, d = v[j].w - m;
-      q += (a * a + b * b) + (c2 * c2 + d * d);
-    }
-  const float r = rsqrtf(wave_sum(q) / D + eps);
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const int c = lane + 64 * j;
-    if (c < D4) {
-      const float4 g4 = reinterpret_cast<const float4*>(gamma)[c], b4 = reinterpret_cast<const float4*>(beta)[c];
-      reinterpret_cast<bf16x4*>(y + row * D)[c] = bf16x4{f2bf((v[j].x - m) * r * g4.x + b4.x), f2bf((v[j].y - m) * r * g4.y + b4.y),
-                                                         f2bf((v[j].z - m) * r * g4.z + b4.z), f2bf((v[j].w - m) * r * g4.w + b4.w)};
-    }
-  }
-  if (lane == 0) { mean[row] = m; rstd[row] = r; }
-}
-// dx (+)= d LayerNorm; pg / pb [nblk][D]: per-workgroup (4 rows) partial sums of dy * xhat and dy, written with plain stores
-__global__ __launch_bounds__(TPB) void k_layernorm_bwd(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ gamma,
-                                                       const float* __restrict__ mean, const float* __restrict__ rstd, int64_t rows, int D,
-                                                       float* __restrict__ dx, int accumulate, float* __restrict__ pg, float* __restrict__ pb,
-                                                       int rows_per_block, const float* __restrict__ extra) {
-  extern __shared__ float sh[];                     // [4 waves][2][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* ag = sh + (size_t)wave * 2 * D;
-  float* ab = ag + D;
-  for (int i = lane; i < D; i += 64) { ag[i] = 0.f; ab[i] = 0.f; }
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  for (int64_t row = r0 + wave; row < r0 + rows_per_block && row < rows; row += TPB / 64) {
-    const float m = mean[row], r = rstd[row];
-    const float* xr = x + row * D;
-    const float* dr = dy + row * D;
-    float s1 = 0.f, s2 = 0.f;
-    for (int i = lane; i < D; i += 64) {
-      const float xh = (xr[i] - m) * r, d = dr[i] * gamma[i];
-      s1 += d; s2 += d * xh;
-      ag[i] += dr[i] * xh; ab[i] += dr[i];          // a lane owns its columns: no conflict inside the wave
-    }
-    s1 = wave_sum(s1) / D; s2 = wave_sum(s2) / D;
-    for (int i = lane; i < D; i += 64) {
-      const float xh = (xr[i] - m) * r;
-      const float v = r * (dr[i] * gamma[i] - s1 - xh * s2);
-      float* o = dx + row * D + i;
-      if (extra) { const float e = extra[row * D + i]; *o = v + (accumulate ? *o + e : e); }     // (dx + extra) + this layer's gradient
-      else *o = accumulate ? *o + v : v;
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < D; i += TPB) {
-    float a = 0.f, b = 0.f;
-    for (int w = 0; w < TPB / 64; ++w) { a += sh[(size_t)w * 2 * D + i]; b += sh[(size_t)w * 2 * D + D + i]; }
-    pg[(size_t)blockIdx.x * D + i] = a; pb[(size_t)blockIdx.x * D + i] = b;
-  }
-}
-// the same with the row and the per-column accumulators in registers, a lane owning float4 column chunks (16-byte loads): x and dy are
-// read once, nothing but the final per-wave sums goes through LDS.
-template <int NC>      // float4 chunks per lane: D <= 256 * NC, D % 4 == 0
-__global__ __launch_bounds__(TPB) void k_layernorm_bwd_r(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ gamma,
-                                                         const float* __restrict__ mean, const float* __restrict__ rstd, int64_t rows, int D,
-                                                         float* __restrict__ dx, int accumulate, float* __restrict__ pg, float* __restrict__ pb,
-                                                         int rows_per_block, const float* __restrict__ extra) {
-  extern __shared__ float sh[];                     // [4 waves][2][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, D4 = D >> 2;
-  float4 ag[NC], ab[NC], gm[NC];
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    ag[j] = make_float4(0.f, 0.f, 0.f, 0.f); ab[j] = ag[j];
-    const int c = lane + 64 * j;
-    gm[j] = c < D4 ? reinterpret_cast<const float4*>(gamma)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  for (int64_t row = r0 + wave; row < r0 + rows_per_block && row < rows; row += TPB / 64) {
-    const float m = mean[row], r = rstd[row];
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    const float4* dr = reinterpret_cast<const float4*>(dy + row * D);
-    float4 xh[NC], dv[NC];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      const int c = lane + 64 * j;
-      const bool in = c < D4;
-      const float4 xv = in ? xr[c] : make_float4(m, m, m, m);
-      dv[j] = in ? dr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-      xh[j] = make_float4((xv.x - m) * r, (xv.y - m) * r, (xv.z - m) * r, (xv.w - m) * r);
-      // the order of k_layernorm_bwd within a lane differs (columns grouped by fours): sums are fixed-order, results reproducible
-      const float d0 = dv[j].x * gm[j].x, d1 = dv[j].y * gm[j].y, d2 = dv[j].z * gm[j].z, d3 = dv[j].w * gm[j].w;
-      s1 += (d0 + d1) + (d2 + d3);
-      s2 += (d0 * xh[j].x + d1 * xh[j].y) + (d2 * xh[j].z + d3 * xh[j].w);
-      ag[j].x += dv[j].x * xh[j].x; ag[j].y += dv[j].y * xh[j].y; ag[j].z += dv[j].z * xh[j].z; ag[j].w += dv[j].w * xh[j].w;
-      ab[j].x += dv[j].x; ab[j].y += dv[j].y; ab[j].z += dv[j].z; ab[j].w += dv[j].w;
-    }
-    s1 = wave_sum(s1) / D; s2 = wave_sum(s2) / D;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      const int c = lane + 64 * j;
-      if (c < D4) {
-        float4 v = make_float4(r * (dv[j].x * gm[j].x - s1 - xh[j].x * s2), r * (dv[j].y * gm[j].y - s1 - xh[j].y * s2),
-                               r * (dv[j].z * gm[j].z - s1 - xh[j].z * s2), r * (dv[j].w * gm[j].w - s1 - xh[j].w * s2));
-        float4* o = reinterpret_cast<float4*>(dx + row * D) + c;
-        if (extra) {                 // (dx + extra) + this layer's gradient: the bits of a separate dx (+)= extra pass before this one
-          float4 e = reinterpret_cast<const float4*>(extra + row * D)[c];
-          if (accumulate) { const float4 p = *o; e.x += p.x; e.y += p.y; e.z += p.z; e.w += p.w; }
-          v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w;
-        } else if (accumulate) { const float4 p = *o; v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w; }
-        *o = v;
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const int c = lane + 64 * j;
-    if (c < D4) {
-      reinterpret_cast<float4*>(sh + (size_t)wave * 2 * D)[c] = ag[j];
-      reinterpret_cast<float4*>(sh + (size_t)wave * 2 * D + D)[c] = ab[j];
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < D; i += TPB) {
-    float a = 0.f, b = 0.f;
-    for (int w = 0; w < TPB / 64; ++w) { a += sh[(size_t)w * 2 * D + i]; b += sh[(size_t)w * 2 * D + D + i]; }
-    pg[(size_t)blockIdx.x * D + i] = a; pb[(size_t)blockIdx.x * D + i] = b;
-  }
-}
-// GEGLU (attention.py:37-45): h [rows][2F] = value || gate -> out = bf16(value * gelu(gate)), exact (erf) GELU as F.gelu
-__global__ __launch_bounds__(TPB) void k_geglu_fwd(const float* __restrict__ h, int64_t rows, int F, __bf16* __restrict__ out) {
-  const int64_t n = rows * F;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int64_t r = i / F; const int c = (int)(i % F);
-    const float a = h[r * 2 * F + c], gt = h[r * 2 * F + F + c];
-    out[i] = f2bf(a * 0.5f * gt * (1.0f + erff(gt * 0.70710678118654752f)));
-  }
-}
-// dh [rows][2F] bf16: d value = d_out * gelu(gate), d gate = d_out * value * gelu'(gate)
-__global__ __launch_bounds__(TPB) void k_geglu_bwd(const float* __restrict__ d_out, const float* __restrict__ h, int64_t rows, int F,
-                                                   __bf16* __restrict__ dh) {
-  const int64_t n = rows * F;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int64_t r = i / F; const int c = (int)(i % F);
-    const float a = h[r * 2 * F + c], gt = h[r * 2 * F + F + c], d = d_out[i];
-    const float cdf = 0.5f * (1.0f + erff(gt * 0.70710678118654752f));
-    const float pdf = 0.3989422804014327f * expf(-0.5f * gt * gt);
-    dh[r * 2 * F + c] = f2bf(d * gt * cdf);
-    dh[r * 2 * F + F + c] = f2bf(d * a * (cdf + gt * pdf));
-  }
-}
-// the same on float4 column quads, rows walked by the workgroup's y index (no per-element 64-bit division): F % 4 == 0
-__global__ __launch_bounds__(TPB) void k_geglu_fwd4(const float* __restrict__ h, int64_t rows, int F, int rows_per_block, __bf16* __restrict__ out) {
-  const int c = (blockIdx.x * TPB + threadIdx.x) * 4;
-  if (c >= F) return;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  for (int64_t r = r0; r < r1; ++r) {
-    const float4 a = *reinterpret_cast<const float4*>(h + r * 2 * F + c), gt = *reinterpret_cast<const float4*>(h + r * 2 * F + F + c);
-    const float av[4] = {a.x, a.y, a.z, a.w}, gv[4] = {gt.x, gt.y, gt.z, gt.w};
-    bf16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(av[e] * 0.5f * gv[e] * (1.0f + erff(gv[e] * 0.70710678118654752f)));
-    *reinterpret_cast<bf16x4*>(out + r * F + c) = o;
-  }
-}
-__global__ __launch_bounds__(TPB) void k_geglu_bwd4(const float* __restrict__ d_out, const float* __restrict__ h, int64_t rows, int F, int rows_per_block,
-                                                    __bf16* __restrict__ dh) {
-  const int c = (blockIdx.x * TPB + threadIdx.x) * 4;
-  if (c >= F) return;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  for (int64_t r = r0; r < r1; ++r) {
-    const float4 a = *reinterpret_cast<const float4*>(h + r * 2 * F + c), gt = *reinterpret_cast<const float4*>(h + r * 2 * F + F + c);
-    const float4 d4 = *reinterpret_cast<const float4*>(d_out + r * F + c);
-    const float av[4] = {a.x, a.y, a.z, a.w}, gv[4] = {gt.x, gt.y, gt.z, gt.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
-    bf16x4 o1, o2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float cdf = 0.5f * (1.0f + erff(gv[e] * 0.70710678118654752f));
-      const float pdf = 0.3989422804014327f * expf(-0.5f * gv[e] * gv[e]);
-      o1[e] = f2bf(dv[e] * gv[e] * cdf);
-      o2[e] = f2bf(dv[e] * av[e] * (cdf + gv[e] * pdf));
-    }
-    *reinterpret_cast<bf16x4*>(dh + r * 2 * F + c) = o1;
-    *reinterpret_cast<bf16x4*>(dh + r * 2 * F + F + c) = o2;
-  }
-}
 
 // finish of a batched split-K product: out[y][z][m][n] (bf16, strides sC / sC2 / ldc) = sum_s slab[s][y][z][m][n]
 __global__ __launch_bounds__(TPB) void k_bsplit_finish(const float* __restrict__ slabs, int nsplit, int ny, int nz, int M, int N, __bf16* __restrict__ out,
@@ -1946,205 +867,6 @@ __global__ __launch_bounds__(TPB) void k_split_finish4(const float* __restrict__
     if (of) *reinterpret_cast<float4*>(of + (int64_t)r * ldo + c) = a;
     else *reinterpret_cast<bf16x4*>(ob + (int64_t)r * ldo + c) = bf16x4{f2bf(a.x), f2bf(a.y), f2bf(a.z), f2bf(a.w)};
   }
-}
-
-// ---- small pieces
-// out[b][c] = sum_{p < HW} x[(b * HW + p) * ld + c]  (per-sample column sums: gradient of a per-sample broadcast vector)
-// one workgroup per (64-column slice, sample): the 4 waves stride over the rows (coalesced 256-B row reads), partial sums meet in LDS
-// in a fixed order
-// gridDim.z row chunks per sample (chunk z takes rows [HW z / nz, HW (z + 1) / nz)): with nz > 1 `out` is the partial buffer
-// [B][nz][C] (ldo = C) that k_reduce_chunks adds per sample in a fixed order
-__global__ __launch_bounds__(TPB) void k_sample_colsum(const float* __restrict__ x, int ld, int HW, int C, float* __restrict__ out, int ldo) {
-  __shared__ float sh[TPB / 64][64];
-  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  const int nz = gridDim.z, z = blockIdx.z;
-  const int p0 = (int)((long)HW * z / nz), p1 = (int)((long)HW * (z + 1) / nz);
-  float s = 0.f;
-  if (c < C) {
-    const float* xb = x + (size_t)b * HW * ld + c;
-    for (int p = p0 + wave; p < p1; p += TPB / 64) s += xb[(size_t)p * ld];
-  }
-  sh[wave][lane] = s;
-  __syncthreads();
-  if (wave == 0 && c < C) {
-    float a = 0.f;
-    for (int w = 0; w < TPB / 64; ++w) a += sh[w][lane];
-    out[((size_t)b * nz + z) * ldo + c] = a;
-  }
-}
-// out = alpha * a + beta * b   (classifier-free guidance mix (1 + s) cond - s null, models/diffusion.py:340-357)
-__global__ __launch_bounds__(TPB) void k_axpby(const float* __restrict__ a, const float* __restrict__ b, float alpha, float beta, int64_t n,
-                                               float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) out[i] = alpha * a[i] + beta * b[i];
-}
-// nearest x2 upsampling backward: dx[b][h][w][c] (+)= sum of the 2x2 block of dy ([B][2H][2W][C])
-__global__ __launch_bounds__(TPB) void k_pool2_sum(const float* __restrict__ dy, int B, int H, int W, int C, float* __restrict__ dx, int accumulate) {
-  const int64_t n = (int64_t)B * H * W * C;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int c = (int)(i % C); int64_t p = i / C; const int w = (int)(p % W); p /= W; const int h = (int)(p % H); const int b = (int)(p / H);
-    const float* s = dy + (((int64_t)b * 2 * H + 2 * h) * 2 * W + 2 * w) * C + c;
-    const float v = s[0] + s[C] + s[(int64_t)2 * W * C] + s[(int64_t)2 * W * C + C];
-    dx[i] = accumulate ? dx[i] + v : v;
-  }
-}
-__global__ __launch_bounds__(TPB) void k_cast_rows(const float* __restrict__ x, int ldx, int64_t rows, int C, __bf16* __restrict__ y) {
-  const int64_t n = rows * C;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
-    y[i] = f2bf(x[(i / C) * ldx + (i % C)]);
-}
-// the same with a lane per float4 of a row (no per-element division), optionally with the column sums of x (the bias gradient of
-// the layer whose output gradient is being cast): grid = (ceil(C / 256), row chunks); the 4 waves of a workgroup take rows
-// r0 + wave, + 4, ... and meet in LDS in a fixed order; partials[chunk][C] are added by k_reduce_chunks
-template <bool SUM>
-__global__ __launch_bounds__(TPB) void k_cast_rows4(const float* __restrict__ x, int ldx, int64_t rows, int C, int rows_per_block,
-                                                    __bf16* __restrict__ y, float* __restrict__ partials) {
-  __shared__ float sh[3][4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = (blockIdx.x * 64 + lane) * 4;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (col < C)
-    for (int64_t r = r0 + wave; r < r1; r += TPB / 64) {
-      const float4 v = *reinterpret_cast<const float4*>(x + r * ldx + col);
-      *reinterpret_cast<bf16x4*>(y + r * C + col) = bf16x4{f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w)};
-      if (SUM) { a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w; }
-    }
-  if (!SUM) return;
-  if (wave > 0) { sh[wave - 1][0][lane] = a0; sh[wave - 1][1][lane] = a1; sh[wave - 1][2][lane] = a2; sh[wave - 1][3][lane] = a3; }
-  __syncthreads();
-  if (wave == 0 && col < C) {
-    float* o = partials + (size_t)blockIdx.y * C + col;
-    o[0] = ((a0 + sh[0][0][lane]) + sh[1][0][lane]) + sh[2][0][lane];
-    o[1] = ((a1 + sh[0][1][lane]) + sh[1][1][lane]) + sh[2][1][lane];
-    o[2] = ((a2 + sh[0][2][lane]) + sh[1][2][lane]) + sh[2][2][lane];
-    o[3] = ((a3 + sh[0][3][lane]) + sh[1][3][lane]) + sh[2][3][lane];
-  }
-}
-__global__ __launch_bounds__(TPB) void k_copy_cols4(const float* __restrict__ x, int ldx, int64_t rows, int C, float* __restrict__ y, int ldy,
-                                                    int accumulate, int rows_per_block) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = (blockIdx.x * 64 + lane) * 4;
-  if (col >= C) return;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  for (int64_t r = r0 + wave; r < r1; r += TPB / 64) {
-    float4 v = *reinterpret_cast<const float4*>(x + r * ldx + col);
-    float4* o = reinterpret_cast<float4*>(y + r * ldy + col);
-    if (accumulate) { const float4 c = *o; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-    *o = v;
-  }
-}
-// Two column copies in ONE launch (blockIdx.z = piece): the channel concatenation torch.cat([h, skip], dim=1) of the up path (two sources into
-// the column halves of one destination) and its backward (the column halves of one source into two gradient buffers, each with its own
-// accumulate flag) were two launches of k_copy_cols4 each -- 5 us apiece on a chain that is bound by its launch count.
-struct CopyPiece { const float* x; int ldx; float* y; int ldy; int C; int accumulate; };
-__global__ __launch_bounds__(TPB) void k_copy_cols4x2(CopyPiece p0, CopyPiece p1, int64_t rows, int rows_per_block) {
-  const CopyPiece p = blockIdx.z ? p1 : p0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = (blockIdx.x * 64 + lane) * 4;
-  if (col >= p.C) return;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  for (int64_t r = r0 + wave; r < r1; r += TPB / 64) {
-    float4 v = *reinterpret_cast<const float4*>(p.x + r * p.ldx + col);
-    float4* o = reinterpret_cast<float4*>(p.y + r * p.ldy + col);
-    if (p.accumulate) { const float4 c = *o; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-    *o = v;
-  }
-}
-// Bernoulli keep mask of nn.Dropout(p) in one launch (torch.rand >= p -> uint8 takes three): element i of mask (seed, call, salt) is
-// kept when 16 bits of splitmix64(seed, counter, salt, i / 4) reach p * 65536.  `counter` lives on the device and is advanced by the
-// caller once per pass, so a captured graph draws fresh masks at every replay.
-__global__ __launch_bounds__(TPB) void k_dropout_mask(uint64_t seed, const int64_t* __restrict__ counter, int64_t salt, int64_t n, unsigned thresh16,
-                                                      uint8_t* __restrict__ out) {
-  const uint64_t base = seed ^ ((uint64_t)counter[0] * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)salt * 0xD1B54A32D192ED03ull);
-  const int64_t nq = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < nq; i += (int64_t)gridDim.x * TPB) {
-    uint64_t z = base + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    uchar4 m;
-    m.x = (unsigned)(z & 0xffff) >= thresh16; m.y = (unsigned)((z >> 16) & 0xffff) >= thresh16;
-    m.z = (unsigned)((z >> 32) & 0xffff) >= thresh16; m.w = (unsigned)(z >> 48) >= thresh16;
-    if (4 * i + 3 < n) *reinterpret_cast<uchar4*>(out + 4 * i) = m;
-    else { const uint8_t e[4] = {m.x, m.y, m.z, m.w}; for (int k = 0; 4 * i + k < n; ++k) out[4 * i + k] = e[k]; }
-  }
-}
-// Every dropout mask of a pass in ONE launch: item j = mask (salt, n elements) at byte offset `off` of one buffer (int64 triples [salt, n, off],
-// off % 4 == 0); blockIdx.y = item.  Bit for bit the masks k_dropout_mask draws for the same (seed, counter, salt): a U-Net pass asked for one
-// launch per ResnetBlock (44 launches of 5 us per DDPM SFR-on step).
-__global__ __launch_bounds__(TPB) void k_dropout_mask_batch(uint64_t seed, const int64_t* __restrict__ counter, const int64_t* __restrict__ items,
-                                                            unsigned thresh16, uint8_t* __restrict__ base_out) {
-  const int64_t salt = items[3 * blockIdx.y], n = items[3 * blockIdx.y + 1];
-  uint8_t* const out = base_out + items[3 * blockIdx.y + 2];
-  const uint64_t base = seed ^ ((uint64_t)counter[0] * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)salt * 0xD1B54A32D192ED03ull);
-  const int64_t nq = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < nq; i += (int64_t)gridDim.x * TPB) {
-    uint64_t z = base + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    uchar4 m;
-    m.x = (unsigned)(z & 0xffff) >= thresh16; m.y = (unsigned)((z >> 16) & 0xffff) >= thresh16;
-    m.z = (unsigned)((z >> 32) & 0xffff) >= thresh16; m.w = (unsigned)(z >> 48) >= thresh16;
-    if (4 * i + 3 < n) *reinterpret_cast<uchar4*>(out + 4 * i) = m;
-    else { const uint8_t e[4] = {m.x, m.y, m.z, m.w}; for (int k = 0; 4 * i + k < n; ++k) out[4 * i + k] = e[k]; }
-  }
-}
-// y[rows][ld_y] column slice <- x[rows][C] (channel concatenation) and back (+=)
-__global__ __launch_bounds__(TPB) void k_copy_cols(const float* __restrict__ x, int ldx, int64_t rows, int C, float* __restrict__ y, int ldy,
-                                                   int accumulate) {
-  const int64_t n = rows * C;
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int64_t r = i / C; const int c = (int)(i % C);
-    float* o = y + r * ldy + c;
-    const float v = x[r * ldx + c];
-    *o = accumulate ? *o + v : v;
-  }
-}
-// DDPM get_timestep_embedding (models/diffusion.py:17-35): sin || cos, freq_j = exp(-ln(1e4) * j / (half - 1)); t is float
-__global__ __launch_bounds__(TPB) void k_ddpm_temb(const float* __restrict__ t, int n, int dim, __bf16* __restrict__ out) {
-  const int half = dim / 2;
-  const float e = logf(10000.0f) / (float)(half - 1);
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n * dim; i += gridDim.x * TPB) {
-    const int b = i / dim, j = i % dim;
-    float v = 0.f;
-    if (j < 2 * half) {
-      const int jj = j < half ? j : j - half;
-      const float a = t[b] * expf(-e * (float)jj);
-      v = j < half ? sinf(a) : cosf(a);
-    }
-    out[i] = f2bf(v);
-  }
-}
-// cemb_in[b] = keep[b] ? table[c[b]] : null_emb   (models/diffusion.py:370-376); labels outside the table read the null row
-__global__ __launch_bounds__(TPB) void k_class_embed(const float* __restrict__ table, const float* __restrict__ null_emb,
-                                                     const int64_t* __restrict__ c, const uint8_t* __restrict__ keep, int n_classes,
-                                                     int n, int D, __bf16* __restrict__ out) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n * D; i += gridDim.x * TPB) {
-    const int b = i / D, j = i % D;
-    const int64_t lab = c[b];
-    const bool use = (!keep || keep[b]) && lab >= 0 && lab < n_classes;
-    out[i] = f2bf(use ? table[lab * D + j] : null_emb[j]);
-  }
-}
-// d_table[c[b]] += d[b] (kept samples), d_null += d[b] (dropped): serial over the batch per column (deterministic)
-__global__ __launch_bounds__(TPB) void k_class_embed_bwd(const float* __restrict__ d, const int64_t* __restrict__ c,
-                                                         const uint8_t* __restrict__ keep, int n_classes, int n, int D,
-                                                         float* __restrict__ d_table, float* __restrict__ d_null) {
-  const int j = blockIdx.x * TPB + threadIdx.x;
-  if (j >= D) return;
-  float nul = 0.f;
-  for (int b = 0; b < n; ++b) {
-    const int64_t lab = c[b];
-    const bool use = (!keep || keep[b]) && lab >= 0 && lab < n_classes;
-    const float g = d[(size_t)b * D + j];
-    if (use) d_table[lab * D + j] += g; else nul += g;
-  }
-  d_null[j] = nul;
 }
 
 // splits of the contraction for a weight-gradient GEMM: enough workgroups for the chip (about two rounds of 256 CUs), at least
@@ -2242,6 +964,7 @@ int launch_cgemm_tt(const BGemmArgs& g, size_t p_bytes, size_t q_bytes, unsigned
   return (g_conv_loader_waves & 2) && nk >= 8 ? launch_cgemm_tt_nl<P_TR, CONVP, SWAP, EPI, 4>(g, p_bytes, q_bytes, mw, mh, nsplit, s)
                                               : launch_cgemm_tt_nl<P_TR, CONVP, SWAP, EPI, 0>(g, p_bytes, q_bytes, mw, mh, nsplit, s);
 }
+// eligibility bound of the pipelined tiles' buffer resources: 16 bytes below the entry points' refusal line (common.h sfron_fits31)
 inline bool fits31(size_t b) { return b < 0x7ffffff0ull; }
 // Linear input gradient (A direct [M][K], B read transposed [K][N]) on the pipelined tile; -1 = not eligible
 int try_cgemm_dt(const BGemmArgs& g, hipStream_t s) {
@@ -2566,214 +1289,7 @@ int sfron_conv_wgrad_scatter_batch(const sfron_wgrad_scatter_item* items, int n_
   return SFRON_OK;
 }
 
-int sfron_nchw_to_rows_bf16(const float* x, int B, int C, int HW, int c_pad, uint16_t* rows, void* stream) {
-  SFRON_CHECK_ARG(x && rows && c_pad >= C);
-  hipLaunchKernelGGL(k_nchw_to_rows, dim3(grid_for((int64_t)B * HW * c_pad)), dim3(TPB), 0, (hipStream_t)stream, x, B, C, HW, c_pad, (__bf16*)rows);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_image_u8_to_rows_bf16(const uint8_t* img, int B, int H, int W, const uint8_t* flip, int c_pad, uint16_t* rows, void* stream) {
-  SFRON_CHECK_ARG(img && rows && B > 0 && H > 0 && W > 0 && c_pad >= 8 && c_pad % 8 == 0 && ((uintptr_t)rows & 15) == 0);
-  hipLaunchKernelGGL(k_image_u8_to_rows, dim3(grid_for((int64_t)B * H * W)), dim3(TPB), 0, (hipStream_t)stream, img, B, H, W, flip, c_pad,
-                     (__bf16*)rows);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_nchw_to_rows_f32(const float* x, int B, int C, int HW, int ld, float* rows, void* stream) {
-  SFRON_CHECK_ARG(x && rows && ld >= C);
-  hipLaunchKernelGGL(k_nchw_to_rows_f32, dim3(grid_for((int64_t)B * HW * ld)), dim3(TPB), 0, (hipStream_t)stream, x, B, C, HW, ld, rows);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int mode, float lo, float hi, int nrow, int padding, int b0, int n,
-                           uint8_t* out, void* stream) {
-  SFRON_CHECK_ARG(rows && out && ld >= 3 && B > 0 && H > 0 && W > 0 && (mode == SFRON_IMAGE_SAVE_IMAGE || mode == SFRON_IMAGE_ROUND || mode == SFRON_IMAGE_TRUNC));
-  SFRON_CHECK_ARG(nrow >= 0 && padding >= 0 && b0 >= 0 && n >= b0 + B && (mode != SFRON_IMAGE_SAVE_IMAGE || hi > lo));
-  int xmaps = 0, pad = 0;
-  int64_t Hc, Wc;
-  if (nrow > 0 && n > 1) {                      // make_grid: n == 1 returns the image itself
-    xmaps = nrow < n ? nrow : n;
-    const int ymaps = (n + xmaps - 1) / xmaps;
-    pad = padding;
-    Hc = (int64_t)ymaps * (H + pad) + pad; Wc = (int64_t)xmaps * (W + pad) + pad;
-  } else if (nrow > 0) {
-    xmaps = 1; Hc = H; Wc = W;                  // one cell, no border (b0 == 0, B == 1)
-  } else {
-    Hc = (int64_t)B * H; Wc = W;                // the B samples of this launch
-  }
-  SFRON_CHECK_ARG(Hc * Wc * 3 < (1ll << 31) && Hc < (1 << 30) && Wc < (1 << 30));
-  hipLaunchKernelGGL(k_rows_to_image_u8, dim3(grid_for(Hc * Wc)), dim3(TPB), 0, (hipStream_t)stream, rows, ld, B, H, W, mode, lo, hi, xmaps,
-                     pad, (int)Hc, (int)Wc, b0, n, out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_rows_to_nchw(const float* rows, int ld, int B, int C, int HW, float* x, void* stream) {
-  SFRON_CHECK_ARG(x && rows && ld >= C);
-  hipLaunchKernelGGL(k_rows_to_nchw, dim3(grid_for((int64_t)B * C * HW)), dim3(TPB), 0, (hipStream_t)stream, rows, ld, B, C, HW, x);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-// debug build only (tools/ A-B runs): SFRON_GN_ONE_LAUNCH=0 in the environment keeps every GroupNorm on the two-phase pair
-static bool gn3_off() {
-#ifdef SFRON_DEBUG_KNOBS
-  static const bool v = [] { const char* e = getenv("SFRON_GN_ONE_LAUNCH"); return e && e[0] == '0'; }();
-  return v;
-#else
-  return false;
-#endif
-}
-/* scratch (bytes) the row-coalesced GroupNorm needs for a [B][HW][C] activation: per-chunk partial sums (forward fp64 per group,
- * backward fp32 per channel) */
-int64_t sfron_groupnorm_scratch_bytes(int B, int HW, int C, int groups) {
-  if (B <= 0 || HW <= 0 || C <= 0 || groups <= 0) return 0;
-  const int64_t n = gn_chunks(B, HW);
-  const int64_t f = (int64_t)B * n * groups * 2 * sizeof(double), bw = (int64_t)B * n * C * 2 * sizeof(float);
-  return f > bw ? f : bw;
-}
-// 2 GiB rule for the GroupNorm family: the kernels step through x / y / dy / dx with size_t offsets, but the chunk and workgroup
-// bookkeeping (B * chunks, rows per chunk) is `int` and nothing runs them above the line -- a [B][HW][ld] fp32 activation of 2^31 bytes
-// or more is refused (its bf16 result is half that)
-static bool gn_fits31(int B, int HW, int ld) { return sfron_fits31((int64_t)B * HW * ld * 4); }
-static bool gn2_ok(int ldx, int ld2, int C, int groups, const void* scratch) {
-  return scratch && C % 4 == 0 && ldx % 4 == 0 && ld2 % 4 == 0 && C <= GN_MAXQ * 4 * GNB && groups <= 64 && ((uintptr_t)scratch & 15) == 0;
-}
-// groups per workgroup of the one-launch form (k_gn3_*), 0 = the two-phase pair: whole groups whose channels form float4 quads and runs that are
-// multiples of half a cache line (a 96-byte run straddles lines: measured 1.7x slower than the pair), at least 192 workgroups, and a slab of at
-// most 128 KB per workgroup (its second pass is an L2 hit) -- or, with eight groups in whole-line runs, up to 512 KB (second pass from the
-// Infinity Cache, as the pair's)
-static int gn3_gpb(int B, int HW, int C, int groups) {
-  if (gn3_off()) return 0;
-  const int cg = C / groups;
-  for (const int gpb : {8, 4, 2, 1}) {
-    if (groups % gpb) continue;
-    const int Cs = gpb * cg;
-    if (Cs % 16 || Cs > 1024) continue;
-    if ((int64_t)HW * Cs * 4 > (128 << 10)) continue;
-    if ((int64_t)B * (groups / gpb) < 192) continue;
-    return gpb;
-  }
-  if (groups % 8 == 0) {
-    const int Cs = 8 * cg;
-    if (Cs % 32 == 0 && Cs <= 1024 && (int64_t)HW * Cs * 4 <= (512 << 10) && (int64_t)B * (groups / 8) >= 192) return 8;
-  }
-  return 0;
-}
-static size_t gn2_lds(int C, int elem) {
-  const int qpr = C / 4, qw = qpr < GNB ? qpr : GNB, rpp = GNB / qw;
-  return (size_t)rpp * C * 2 * elem;
-}
-int sfron_groupnorm_fwd(const float* x, int ldx, const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps,
-                        int swish, const uint8_t* drop_mask, float drop_scale, uint16_t* y, float* mean, float* rstd, void* scratch,
-                        void* stream) {
-  SFRON_CHECK_ARG(x && gamma && beta && y && mean && rstd && groups > 0 && C % groups == 0 && ldx >= C && C / groups <= TPB);
-  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
-  if (gn2_ok(ldx, C, C, groups, scratch) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0)) {
-    if (const int gpb = gn3_gpb(B, HW, C, groups)) {
-      hipLaunchKernelGGL(k_gn3_fwd<false>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, x, ldx, gamma, beta, HW, C, groups, gpb, eps, swish,
-                         drop_mask, drop_scale, (__bf16*)y, mean, rstd, Gn3Src{});
-      SFRON_LAUNCH_STATUS();
-      return SFRON_OK;
-    }
-    const int nchunk = gn_chunks(B, HW);
-    hipLaunchKernelGGL(k_gn2_stats, dim3(B * nchunk), dim3(GNB), gn2_lds(C, sizeof(double)), (hipStream_t)stream, x, ldx, HW, C, groups, nchunk,
-                       (double*)scratch);
-    SFRON_LAUNCH_STATUS();
-    hipLaunchKernelGGL(k_gn2_apply, dim3(B * nchunk), dim3(GNB), 0, (hipStream_t)stream, x, ldx, gamma, beta, HW, C, groups, eps, swish, drop_mask,
-                       drop_scale, nchunk, (const double*)scratch, (__bf16*)y, mean, rstd);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_gn_fwd, dim3(B * groups), dim3(TPB), 0, (hipStream_t)stream, x, ldx, gamma, beta, HW, C, groups, eps, swish, drop_mask,
-                     drop_scale, (__bf16*)y, mean, rstd);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_groupnorm_bwd(const float* dy, const float* x, int ldx, const float* gamma, const float* beta, const float* mean,
-                        const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
-                        float* dx, int lddx, int accumulate, float* part_gamma, float* part_beta, void* scratch, void* stream) {
-  return sfron_groupnorm_bwd_res(dy, x, ldx, gamma, beta, mean, rstd, B, HW, C, groups, swish, drop_mask, drop_scale, dx, lddx, accumulate, nullptr, 0,
-                                 part_gamma, part_beta, scratch, stream);
-}
-int sfron_groupnorm_bwd_res(const float* dy, const float* x, int ldx, const float* gamma, const float* beta, const float* mean,
-                            const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
-                            float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma, float* part_beta,
-                            void* scratch, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0);
-  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
-  const int cg = C / groups;
-  SFRON_CHECK_ARG(cg <= TPB);
-  SFRON_CHECK_ARG(!extra || (ld_extra >= C && extra != dx));
-  const bool fused = gn2_ok(ldx, lddx, C, groups, scratch) && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 &&
-                     (!drop_mask || ((uintptr_t)drop_mask & 3) == 0);
-  if (extra && !(fused && ld_extra % 4 == 0 && ((uintptr_t)extra & 15) == 0)) {       // the same sum as two passes
-    const int rc = sfron_copy_cols(extra, ld_extra, (int64_t)B * HW, C, dx, lddx, accumulate, stream);
-    if (rc) return rc;
-    extra = nullptr; accumulate = 1;
-  }
-  if (fused) {
-    if (const int gpb = gn3_gpb(B, HW, C, groups)) {
-      hipLaunchKernelGGL(k_gn3_bwd<false>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd, HW, C, groups, gpb,
-                         swish, drop_mask, drop_scale, dx, lddx, accumulate, part_gamma, part_beta, extra, ld_extra, (__bf16*)nullptr, (float*)nullptr, 1,
-                         Gn3Src{});
-      SFRON_LAUNCH_STATUS();
-      return SFRON_OK;
-    }
-    const int nchunk = gn_chunks(B, HW);
-    hipLaunchKernelGGL(k_gn2_bwd_stats, dim3(B * nchunk), dim3(GNB), gn2_lds(C, sizeof(float)), (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd,
-                       HW, C, groups, swish, drop_mask, drop_scale, nchunk, (float*)scratch);
-    SFRON_LAUNCH_STATUS();
-    hipLaunchKernelGGL(k_gn2_bwd_apply, dim3(B * nchunk), dim3(GNB), (size_t)(3 * C + 2 * groups) * sizeof(float), (hipStream_t)stream, dy, x, ldx, gamma,
-                       beta, mean, rstd, HW, C, groups, swish, drop_mask, drop_scale, nchunk, (const float*)scratch, dx, lddx, accumulate,
-                       part_gamma, part_beta, extra, ld_extra, (__bf16*)nullptr, (float*)nullptr);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  const size_t lds = (2 * (TPB / 64) + 2 * cg + 2 * TPB) * sizeof(float);
-  hipLaunchKernelGGL(k_gn_bwd, dim3(B * groups), dim3(TPB), lds, (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd, HW, C, groups, swish,
-                     drop_mask, drop_scale, dx, lddx, accumulate, part_gamma, part_beta);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-int sfron_groupnorm_chunks(int B, int HW) { return (B > 0 && HW > 0) ? gn_chunks(B, HW) : 0; }
-int sfron_groupnorm_bwd_cast_ok(int ldx, int C, int groups) {
-  return C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && ldx % 4 == 0 && C <= 2048 && C <= GN_MAXQ * 4 * GNB && groups <= 64;
-}
-int sfron_groupnorm_bwd_cast(const float* dy, const float* x, int ldx, const float* gamma, const float* beta, const float* mean,
-                             const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
-                             uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* scratch, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && scratch);
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
-  SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)scratch) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 &&
-                  (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
-  const int nchunk = gn_chunks(B, HW);
-  if (const int gpb = gn3_gpb(B, HW, C, groups)) {
-    hipLaunchKernelGGL(k_gn3_bwd<false>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd, HW, C, groups, gpb,
-                       swish, drop_mask, drop_scale, (float*)nullptr, C, 0, part_gamma, part_beta, (const float*)nullptr, 0, (__bf16*)dx_bf16,
-                       col_partials, nchunk, Gn3Src{});
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_gn2_bwd_stats, dim3(B * nchunk), dim3(GNB), gn2_lds(C, sizeof(float)), (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd,
-                     HW, C, groups, swish, drop_mask, drop_scale, nchunk, (float*)scratch);
-  SFRON_LAUNCH_STATUS();
-  const size_t lds = (size_t)(3 * C + 2 * groups + 4 * GNB) * sizeof(float);          // + [rows per pass][C] for the column sums
-  hipLaunchKernelGGL(k_gn2_bwd_apply, dim3(B * nchunk), dim3(GNB), lds, (hipStream_t)stream, dy, x, ldx, gamma, beta, mean, rstd, HW, C, groups, swish,
-                     drop_mask, drop_scale, nchunk, (const float*)scratch, (float*)nullptr, C, 0, part_gamma, part_beta, (const float*)nullptr, 0,
-                     (__bf16*)dx_bf16, col_partials);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-// ---- the GroupNorm input as an unfinished split-K result (sfron_split_src)
-static bool split_src_ok(const sfron_split_src* s, int C) {
-  return s && s->slabs && s->n_slabs >= 1 && s->slab_stride > 0 && C % 4 == 0 && (((uintptr_t)s->slabs | (uintptr_t)s->bias | (uintptr_t)s->sample_vec |
-         (uintptr_t)s->resid) & 15) == 0 && s->slab_stride % 4 == 0 && (!s->sample_vec || s->ld_vec % 4 == 0) && (!s->resid || s->ld_resid % 4 == 0);
-}
-static Gn3Src gn3_src(const sfron_split_src* s) {
-  return Gn3Src{s->slabs, s->n_slabs, s->slab_stride, s->bias, s->sample_vec, s->ld_vec, s->resid, s->ld_resid};
-}
+// the plain finish of the slabs sfron_conv_fwd left pending (a GroupNorm that takes them itself: groupnorm.hip sfron_groupnorm_*_src)
 int sfron_split_finish(const sfron_split_src* src, int64_t rows, int C, int rows_per_sample, float* out_f32, uint16_t* out_bf16, int ld_out,
                        void* stream) {
   SFRON_CHECK_ARG(split_src_ok(src, C) && rows > 0 && rows <= 0x7fffffff && rows_per_sample > 0 && ((out_f32 != nullptr) != (out_bf16 != nullptr)) &&
@@ -2786,272 +1302,6 @@ int sfron_split_finish(const sfron_split_src* src, int64_t rows, int C, int rows
   hipLaunchKernelGGL(k_split_finish4, dim3(cb, (unsigned)((rows + rpb - 1) / rpb)), dim3(TPB), 0, (hipStream_t)stream, src->slabs, src->n_slabs,
                      src->slab_stride, (int)rows, C, src->bias, src->sample_vec, src->ld_vec, rows_per_sample, src->resid, out_f32, (__bf16*)out_bf16,
                      ld_out, rpb);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_groupnorm_one_launch(int B, int HW, int C, int groups) {
-  return B > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && groups <= 64 && gn3_gpb(B, HW, C, groups) > 0;
-}
-int sfron_groupnorm_fwd_src(const sfron_split_src* src, float* x, const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps,
-                            int swish, const uint8_t* drop_mask, float drop_scale, uint16_t* y, float* mean, float* rstd, void* stream) {
-  SFRON_CHECK_ARG(x && gamma && beta && y && mean && rstd && groups > 0 && C % groups == 0 && split_src_ok(src, C));
-  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, C));
-  SFRON_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0) && groups <= 64);
-  SFRON_CHECK_ARG(!src->resid || (const float*)x != src->resid);
-  const int gpb = gn3_gpb(B, HW, C, groups);
-  if (!gpb) return SFRON_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_gn3_fwd<true>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, (const float*)x, C, gamma, beta, HW, C, groups, gpb,
-                     eps, swish, drop_mask, drop_scale, (__bf16*)y, mean, rstd, gn3_src(src));
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_groupnorm_bwd_res_src(const sfron_split_src* src, float* dy, const float* x, int ldx, const float* gamma, const float* beta,
-                                const float* mean, const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask,
-                                float drop_scale, float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma,
-                                float* part_beta, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0 && split_src_ok(src, C));
-  SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
-  SFRON_CHECK_ARG(ldx % 4 == 0 && lddx % 4 == 0 && groups <= 64 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 &&
-                  (!drop_mask || ((uintptr_t)drop_mask & 3) == 0) && dy != dx);
-  SFRON_CHECK_ARG(!extra || (ld_extra >= C && extra != dx && ld_extra % 4 == 0 && ((uintptr_t)extra & 15) == 0));
-  const int gpb = gn3_gpb(B, HW, C, groups);
-  if (!gpb) return SFRON_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_gn3_bwd<true>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, (const float*)dy, x, ldx, gamma, beta, mean, rstd, HW,
-                     C, groups, gpb, swish, drop_mask, drop_scale, dx, lddx, accumulate, part_gamma, part_beta, extra, ld_extra, (__bf16*)nullptr,
-                     (float*)nullptr, 1, gn3_src(src));
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_groupnorm_bwd_cast_src(const sfron_split_src* src, float* dy, const float* x, int ldx, const float* gamma, const float* beta,
-                                 const float* mean, const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask,
-                                 float drop_scale, uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && split_src_ok(src, C));
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
-  SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
-  const int gpb = gn3_gpb(B, HW, C, groups);
-  if (!gpb) return SFRON_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_gn3_bwd<true>, dim3(B * (groups / gpb)), dim3(GN3_T), 0, (hipStream_t)stream, (const float*)dy, x, ldx, gamma, beta, mean, rstd, HW,
-                     C, groups, gpb, swish, drop_mask, drop_scale, (float*)nullptr, C, 0, part_gamma, part_beta, (const float*)nullptr, 0,
-                     (__bf16*)dx_bf16, col_partials, gn_chunks(B, HW), gn3_src(src));
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-// No 2 GiB limit: k_softmax_fwd / k_softmax_bwd take the row index as int64_t and form row * n in 64-bit; one wave per row, four rows per
-// workgroup, so the only 32-bit quantity is the grid (rows / 4 < 2^31).  tests/test_gpu_large_shapes.py runs a score matrix above 2 GiB.
-int sfron_softmax_fwd(const float* s, int64_t rows, int n, int n_valid, float scale, uint16_t* p, void* stream) {
-  SFRON_CHECK_ARG(s && p && rows > 0 && n > 0 && n_valid > 0 && n_valid <= n && (rows + 3) / 4 < (1ll << 31));
-  hipLaunchKernelGGL(k_softmax_fwd, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, (hipStream_t)stream, s, rows, n, n_valid, scale, (__bf16*)p);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_layernorm_fwd(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, uint16_t* y, float* mean,
-                        float* rstd, void* stream) {
-  SFRON_CHECK_ARG(x && gamma && beta && y && mean && rstd && rows > 0 && D > 0);
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  const bool v4 = D % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0 && (((uintptr_t)y) & 7) == 0;
-  if (v4 && D <= 512)       hipLaunchKernelGGL(k_layernorm_fwd_r<2>, grid, dim3(TPB), 0, (hipStream_t)stream, x, gamma, beta, rows, D, eps, (__bf16*)y, mean, rstd);
-  else if (v4 && D <= 768)  hipLaunchKernelGGL(k_layernorm_fwd_r<3>, grid, dim3(TPB), 0, (hipStream_t)stream, x, gamma, beta, rows, D, eps, (__bf16*)y, mean, rstd);
-  else if (v4 && D <= 1280) hipLaunchKernelGGL(k_layernorm_fwd_r<5>, grid, dim3(TPB), 0, (hipStream_t)stream, x, gamma, beta, rows, D, eps, (__bf16*)y, mean, rstd);
-  else hipLaunchKernelGGL(k_layernorm_fwd, grid, dim3(TPB), 0, (hipStream_t)stream, x, gamma, beta, rows, D, eps, (__bf16*)y, mean, rstd);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-// rows per workgroup of the backward pass (= rows per partial parameter-gradient row): about 512 workgroups, 16 .. 64 rows each
-int sfron_layernorm_rows_per_block(int64_t rows) {
-  int64_t r = ((rows + 511) / 512 + 3) / 4 * 4;
-  return (int)(r < 16 ? 16 : (r > 64 ? 64 : r));
-}
-int sfron_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, int64_t rows, int D, float* dx,
-                        int accumulate, float* part_gamma, float* part_beta, void* stream) {
-  return sfron_layernorm_bwd_res(dy, x, gamma, mean, rstd, rows, D, dx, accumulate, nullptr, part_gamma, part_beta, stream);
-}
-int sfron_layernorm_bwd_res(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, int64_t rows, int D, float* dx,
-                            int accumulate, const float* extra, float* part_gamma, float* part_beta, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && mean && rstd && dx && part_gamma && part_beta && rows > 0 && D > 0 && D <= 4096);
-  SFRON_CHECK_ARG(extra != dx);
-  const int rpb = sfron_layernorm_rows_per_block(rows);
-  const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
-  const size_t lds = (size_t)(TPB / 64) * 2 * D * sizeof(float);
-  const bool v4 = D % 4 == 0 && ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)gamma) | ((uintptr_t)extra)) & 15) == 0;
-  if (v4 && D <= 512)       hipLaunchKernelGGL(k_layernorm_bwd_r<2>, grid, dim3(TPB), lds, (hipStream_t)stream, dy, x, gamma, mean, rstd, rows, D, dx, accumulate, part_gamma, part_beta, rpb, extra);
-  else if (v4 && D <= 768)  hipLaunchKernelGGL(k_layernorm_bwd_r<3>, grid, dim3(TPB), lds, (hipStream_t)stream, dy, x, gamma, mean, rstd, rows, D, dx, accumulate, part_gamma, part_beta, rpb, extra);
-  else if (v4 && D <= 1280) hipLaunchKernelGGL(k_layernorm_bwd_r<5>, grid, dim3(TPB), lds, (hipStream_t)stream, dy, x, gamma, mean, rstd, rows, D, dx, accumulate, part_gamma, part_beta, rpb, extra);
-  else hipLaunchKernelGGL(k_layernorm_bwd, grid, dim3(TPB), lds, (hipStream_t)stream, dy, x, gamma, mean, rstd, rows, D, dx, accumulate, part_gamma, part_beta, rpb, extra);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_geglu_fwd(const float* h, int64_t rows, int F, uint16_t* out, void* stream) {
-  SFRON_CHECK_ARG(h && out && rows > 0 && F > 0);
-  if (F % 4 == 0 && ((((uintptr_t)h)) & 15) == 0 && (((uintptr_t)out) & 7) == 0) {
-    const int cb = (F / 4 + TPB - 1) / TPB;
-    int64_t chunks = 4096 / cb; if (chunks > rows) chunks = rows; if (chunks < 1) chunks = 1;
-    const int rpb = (int)((rows + chunks - 1) / chunks);
-    hipLaunchKernelGGL(k_geglu_fwd4, dim3(cb, (unsigned)((rows + rpb - 1) / rpb)), dim3(TPB), 0, (hipStream_t)stream, h, rows, F, rpb, (__bf16*)out);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_geglu_fwd, dim3(grid_for(rows * F)), dim3(TPB), 0, (hipStream_t)stream, h, rows, F, (__bf16*)out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_geglu_bwd(const float* d_out, const float* h, int64_t rows, int F, uint16_t* dh, void* stream) {
-  SFRON_CHECK_ARG(d_out && h && dh && rows > 0 && F > 0);
-  if (F % 4 == 0 && ((((uintptr_t)h) | ((uintptr_t)d_out)) & 15) == 0 && (((uintptr_t)dh) & 7) == 0) {
-    const int cb = (F / 4 + TPB - 1) / TPB;
-    int64_t chunks = 4096 / cb; if (chunks > rows) chunks = rows; if (chunks < 1) chunks = 1;
-    const int rpb = (int)((rows + chunks - 1) / chunks);
-    hipLaunchKernelGGL(k_geglu_bwd4, dim3(cb, (unsigned)((rows + rpb - 1) / rpb)), dim3(TPB), 0, (hipStream_t)stream, d_out, h, rows, F, rpb, (__bf16*)dh);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_geglu_bwd, dim3(grid_for(rows * F)), dim3(TPB), 0, (hipStream_t)stream, d_out, h, rows, F, (__bf16*)dh);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-int sfron_softmax_bwd(const uint16_t* p, const float* dp, int64_t rows, int n, float scale, uint16_t* ds, void* stream) {
-  SFRON_CHECK_ARG(p && dp && ds && rows > 0 && n > 0 && (rows + 3) / 4 < (1ll << 31));
-  hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, (hipStream_t)stream, (const __bf16*)p, dp, rows, n, scale, (__bf16*)ds);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-
-int sfron_axpby(const float* a, const float* b, float alpha, float beta, int64_t n, float* out, void* stream) {
-  SFRON_CHECK_ARG(a && b && out);
-  hipLaunchKernelGGL(k_axpby, dim3(grid_for(n)), dim3(TPB), 0, (hipStream_t)stream, a, b, alpha, beta, n, out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_sample_colsum(const float* x, int ld, int B, int HW, int C, float* out, int ld_out, float* scratch, int64_t scratch_floats,
-                        void* stream) {
-  SFRON_CHECK_ARG(x && out && ld_out >= C && B > 0 && HW > 0 && C > 0);
-  // few (column block, sample) pairs and many rows: chunk the rows, partial sums [B][nz][C] in the caller's scratch, fixed-order add
-  int nz = 512 / (((C + 63) / 64) * B);
-  if (nz > 32) nz = 32;
-  if (nz > HW / 16) nz = HW / 16;
-  if (scratch && nz > 1 && (int64_t)B * nz * C <= scratch_floats) {
-    hipLaunchKernelGGL(k_sample_colsum, dim3((C + 63) / 64, B, nz), dim3(TPB), 0, (hipStream_t)stream, x, ld, HW, C, scratch, C);
-    SFRON_LAUNCH_STATUS();
-    return sfron_reduce_chunks(scratch, B, nz, C, out, ld_out, 0, stream);
-  }
-  hipLaunchKernelGGL(k_sample_colsum, dim3((C + 63) / 64, B, 1), dim3(TPB), 0, (hipStream_t)stream, x, ld, HW, C, out, ld_out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_pool2_sum(const float* dy, int B, int H, int W, int C, float* dx, int accumulate, void* stream) {
-  SFRON_CHECK_ARG(dy && dx);
-  hipLaunchKernelGGL(k_pool2_sum, dim3(grid_for((int64_t)B * H * W * C)), dim3(TPB), 0, (hipStream_t)stream, dy, B, H, W, C, dx, accumulate);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-// No 2 GiB limit: k_cast_rows / k_cast_rows4 (and the k_copy_cols family below) carry the row as int64_t and form r * ldx in 64-bit; the
-// row-chunk grid stays below 65536.  tests/test_gpu_large_shapes.py casts an activation above 2 GiB.
-int sfron_cast_rows_bf16(const float* x, int ldx, int64_t rows, int C, uint16_t* y, void* stream) {
-  SFRON_CHECK_ARG(x && y && ldx >= C);
-  if (C % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 7) == 0) {
-    const int rpb = rows_chunk(rows, C);
-    hipLaunchKernelGGL((k_cast_rows4<false>), dim3((C + 255) / 256, (unsigned)((rows + rpb - 1) / rpb)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, rows, C,
-                       rpb, (__bf16*)y, (float*)nullptr);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_cast_rows, dim3(grid_for(rows * C)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, rows, C, (__bf16*)y);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-/* y = bf16(x) and colsum[c] = sum_r x[r][c] in one pass over x (the output gradient of a layer: its bf16 GEMM operand and its bias
- * gradient); partials: scratch of at least max_partials * C floats */
-int sfron_cast_rows_colsum(const float* x, int ldx, int64_t rows, int C, uint16_t* y, float* partials, int max_partials, float* colsum,
-                           void* stream) {
-  SFRON_CHECK_ARG(colsum);
-  int chunks = 0;
-  const int rc = sfron_cast_rows_colsum_partials(x, ldx, rows, C, y, partials, max_partials, &chunks, stream);
-  if (rc) return rc;
-  return sfron_reduce_chunks(partials, 1, chunks, C, colsum, C, 0, stream);
-}
-int sfron_cast_rows_colsum_partials(const float* x, int ldx, int64_t rows, int C, uint16_t* y, float* partials, int max_partials,
-                                    int* chunks_out, void* stream) {
-  SFRON_CHECK_ARG(x && y && partials && chunks_out && rows > 0 && C > 0 && ldx >= C && max_partials > 0);
-  SFRON_CHECK_ARG(C % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 7) == 0);
-  // about 512 workgroups over (column blocks x row chunks), at least 32 rows per chunk, within the caller's scratch
-  int64_t chunks = 512 / ((C + 255) / 256);
-  if (chunks > (rows + 31) / 32) chunks = (rows + 31) / 32;
-  if (chunks > max_partials) chunks = max_partials;
-  if (chunks < 1) chunks = 1;
-  const int rpb = (int)((rows + chunks - 1) / chunks);
-  chunks = (rows + rpb - 1) / rpb;
-  hipLaunchKernelGGL((k_cast_rows4<true>), dim3((C + 255) / 256, (unsigned)chunks), dim3(TPB), 0, (hipStream_t)stream, x, ldx, rows, C, rpb, (__bf16*)y,
-                     partials);
-  SFRON_LAUNCH_STATUS();
-  *chunks_out = (int)chunks;
-  return SFRON_OK;
-}
-int sfron_dropout_mask(uint64_t seed, const int64_t* counter, int64_t salt, int64_t n, float p, uint8_t* mask, void* stream) {
-  SFRON_CHECK_ARG(counter && mask && n > 0 && p >= 0.f && p < 1.f && (((uintptr_t)mask) & 3) == 0);
-  const unsigned thresh = (unsigned)(p * 65536.0f + 0.5f);
-  hipLaunchKernelGGL(k_dropout_mask, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, (hipStream_t)stream, seed, counter, salt, n, thresh, mask);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_dropout_mask_batch(uint64_t seed, const int64_t* counter, const int64_t* items_dev, int n_items, int64_t max_n, float p, uint8_t* mask_base,
-                             void* stream) {
-  SFRON_CHECK_ARG(counter && items_dev && mask_base && n_items > 0 && n_items <= 65535 && max_n > 0 && p >= 0.f && p < 1.f &&
-                  (((uintptr_t)mask_base) & 3) == 0);
-  const unsigned thresh = (unsigned)(p * 65536.0f + 0.5f);
-  int gx = grid_for((max_n + 3) / 4);
-  if (gx > 64) gx = 64;                         // n_items rows of workgroups fill the chip
-  hipLaunchKernelGGL(k_dropout_mask_batch, dim3(gx, n_items), dim3(TPB), 0, (hipStream_t)stream, seed, counter, items_dev, thresh, mask_base);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_copy_cols(const float* x, int ldx, int64_t rows, int C, float* y, int ldy, int accumulate, void* stream) {
-  SFRON_CHECK_ARG(x && y && ldx >= C && ldy >= C);
-  if (C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0) {
-    const int rpb = rows_chunk(rows, C);
-    hipLaunchKernelGGL(k_copy_cols4, dim3((C + 255) / 256, (unsigned)((rows + rpb - 1) / rpb)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, rows, C, y, ldy,
-                       accumulate, rpb);
-    SFRON_LAUNCH_STATUS();
-    return SFRON_OK;
-  }
-  hipLaunchKernelGGL(k_copy_cols, dim3(grid_for(rows * C)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, rows, C, y, ldy, accumulate);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_copy_cols2(const float* x0, int ldx0, int C0, float* y0, int ldy0, int acc0, const float* x1, int ldx1, int C1, float* y1, int ldy1,
-                     int acc1, int64_t rows, void* stream) {
-  SFRON_CHECK_ARG(x0 && y0 && x1 && y1 && rows > 0 && C0 > 0 && C1 > 0 && ldx0 >= C0 && ldy0 >= C0 && ldx1 >= C1 && ldy1 >= C1);
-  const bool wide = ((C0 | C1 | ldx0 | ldx1 | ldy0 | ldy1) & 3) == 0 &&
-                    ((((uintptr_t)x0) | ((uintptr_t)y0) | ((uintptr_t)x1) | ((uintptr_t)y1)) & 15) == 0;
-  if (!wide) {                                   // unaligned shapes: the two plain launches
-    const int rc = sfron_copy_cols(x0, ldx0, rows, C0, y0, ldy0, acc0, stream);
-    return rc != SFRON_OK ? rc : sfron_copy_cols(x1, ldx1, rows, C1, y1, ldy1, acc1, stream);
-  }
-  const int Cm = C0 > C1 ? C0 : C1;
-  const int rpb = rows_chunk(rows, Cm);
-  hipLaunchKernelGGL(k_copy_cols4x2, dim3((Cm + 255) / 256, (unsigned)((rows + rpb - 1) / rpb), 2), dim3(TPB), 0, (hipStream_t)stream,
-                     CopyPiece{x0, ldx0, y0, ldy0, C0, acc0}, CopyPiece{x1, ldx1, y1, ldy1, C1, acc1}, rows, rpb);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_ddpm_timestep_embed(const float* t, int n, int dim, uint16_t* out, void* stream) {
-  SFRON_CHECK_ARG(t && out && dim >= 4);
-  hipLaunchKernelGGL(k_ddpm_temb, dim3(grid_for((int64_t)n * dim)), dim3(TPB), 0, (hipStream_t)stream, t, n, dim, (__bf16*)out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_class_embed_fwd(const float* table, const float* null_emb, const int64_t* c, const uint8_t* keep, int n_classes, int n, int D,
-                          uint16_t* out, void* stream) {
-  SFRON_CHECK_ARG(table && null_emb && c && out);
-  hipLaunchKernelGGL(k_class_embed, dim3(grid_for((int64_t)n * D)), dim3(TPB), 0, (hipStream_t)stream, table, null_emb, c, keep, n_classes, n, D,
-                     (__bf16*)out);
-  SFRON_LAUNCH_STATUS();
-  return SFRON_OK;
-}
-int sfron_class_embed_bwd(const float* d, const int64_t* c, const uint8_t* keep, int n_classes, int n, int D, float* d_table, float* d_null,
-                          void* stream) {
-  SFRON_CHECK_ARG(d && c && d_table && d_null);
-  hipLaunchKernelGGL(k_class_embed_bwd, dim3((D + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, d, c, keep, n_classes, n, D, d_table, d_null);
   SFRON_LAUNCH_STATUS();
   return SFRON_OK;
 }

@@ -51,16 +51,6 @@ __global__ __launch_bounds__(TPB) void k_ddpm_sampler_advance(const float* __res
   if (threadIdx.x == 0) *step = next;
 }
 
-// the SFRON_IMAGE_SAVE_IMAGE byte of csrc/conv.hip's img_u8, operation for operation
-__device__ __forceinline__ uint8_t save_image_u8(float x, float lo, float hi) {
-  const float c = fminf(fmaxf(x, lo), hi);
-  const float v = (c - lo) / (hi - lo);
-  float t = v * 255.0f;
-  t = t + 0.5f;
-  t = fminf(fmaxf(t, 0.0f), 255.0f);
-  return (uint8_t)(int)t;
-}
-
 // One workgroup (4 waves of 64 lanes) per image.  x fp32 [B][3][HW] -> out uint8 [B][HW][3].  Pass 1: min / max of the image's 3 HW values
 // (a strided loop per thread, a 64-lane xor butterfly per wave, the 4 wave results through LDS).  hi = max(hi, lo + 1e-5) is formed in
 // double and rounded once, as sfron.images.make_grid_u8 hands it to sfron_rows_to_image_u8.  Pass 2: one thread per output byte.

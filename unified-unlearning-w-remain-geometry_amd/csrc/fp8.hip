@@ -31,10 +31,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((address_space(3))) void lptr8_t;
 
-constexpr float E4M3_MAX = 448.0f;
 constexpr int TPB = 256;
-
-__device__ __forceinline__ float sat8(float x) { return fminf(fmaxf(x, -E4M3_MAX), E4M3_MAX); }
 
 // ---- how much of the e4m3 range the ACTIVATIONS use: the activation scales are static (engine.py: 8 / 32 / 16), the conversion saturates, and
 // nothing else would tell a run on real weights that its LN + modulate outputs left the range.  Every kernel that quantises an activation
@@ -53,13 +50,6 @@ __device__ __forceinline__ void amax_report(unsigned int* words, int site, float
   // config 5 six ms per step); a stale read of the word can only cause a surplus atomic, never a lost maximum
   if ((threadIdx.x & 63) == 0 && m > __uint_as_float(__builtin_nontemporal_load(&words[site])))
     atomicMax(&words[site], __float_as_uint(m));
-}
-// four fp32 -> four e4m3 bytes (little endian: a in bits 0..7)
-__device__ __forceinline__ uint32_t pack_e4m3(float a, float b, float c, float d) {
-  int v = 0;
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(sat8(a), sat8(b), v, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(sat8(c), sat8(d), v, true);
-  return (uint32_t)v;
 }
 
 // ---- MX (block-scaled) e4m3 of a dY operand: one E8M0 byte per 32 consecutive elements of a row (include/sfron.h states the rule).
@@ -243,9 +233,6 @@ constexpr int NCHQ = 5;            // row chunks of 256 floats: D <= 1280
 // (as norm.hip k_ln_mod_fwd: one-row buffer descriptors -- branch-free --, RPW rows of one sample per wave, every load before the first use,
 // the sample's shift / scale rows fetched once per wave)
 typedef unsigned int q_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t q_row_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 template <int RPW>
 __global__ __launch_bounds__(TPB) void k_ln_mod_fwd_q(const float* __restrict__ x, const float* __restrict__ shift,
                                                       const float* __restrict__ scale, int ldmod, int T, int M, int D,
@@ -258,11 +245,11 @@ __global__ __launch_bounds__(TPB) void k_ln_mod_fwd_q(const float* __restrict__ 
   float4 v[RPW][NCHQ], sh[NCHQ], sc[NCHQ];
   {
     const int b = row0 / T;
-    const __amdgpu_buffer_rsrc_t rh = q_row_rsrc(shift + (size_t)b * ldmod, D * 4), rc = q_row_rsrc(scale + (size_t)b * ldmod, D * 4);
+    const __amdgpu_buffer_rsrc_t rh = row_rsrc(shift + (size_t)b * ldmod, D * 4), rc = row_rsrc(scale + (size_t)b * ldmod, D * 4);
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
       const int row = row0 + k < M ? row0 + k : M - 1;
-      const __amdgpu_buffer_rsrc_t rx = q_row_rsrc(x + (size_t)row * D, D * 4);
+      const __amdgpu_buffer_rsrc_t rx = row_rsrc(x + (size_t)row * D, D * 4);
 #pragma unroll
       for (int i = 0; i < NCHQ; ++i) v[k][i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + 1024 * i, 0, 0));
     }
@@ -290,7 +277,7 @@ __global__ __launch_bounds__(TPB) void k_ln_mod_fwd_q(const float* __restrict__ 
     const float var = wave_sum(q) / (float)D;
     const float rstd = 1.0f / sqrtf(var + 1e-6f);
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
-    const __amdgpu_buffer_rsrc_t ro = q_row_rsrc(out + (size_t)row * D, D * 2), r8 = q_row_rsrc(out8 + (size_t)row * D, D);
+    const __amdgpu_buffer_rsrc_t ro = row_rsrc(out + (size_t)row * D, D * 2), r8 = row_rsrc(out8 + (size_t)row * D, D);
 #pragma unroll
     for (int i = 0; i < NCHQ; ++i) {
       const float4 h = sh[i], g = sc[i];

@@ -13,6 +13,7 @@
 // (8-byte bf16 / 16-byte fp32 stores).  LDS: double-buffered, XOR-swizzled so that both the
 // ds_read_b128 row fragments and the transposed reads are bank-conflict free.
 #include "common.h"
+#include "tile.h"
 #include "../../include/sfron.h"
 
 extern int g_conv_loader_waves;     // conv.hip: k_cgemm
@@ -71,33 +72,6 @@ enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_GATE_RES = 3, EPI_DGELU = 4,
        EPI_QGELU = 9 };     // c_bf16 = quick_gelu(result) = r * sigmoid(1.702 r) (CLIP text encoder fc1; generic kernel and the 128 x 128 tile)
 
 
-
-// ---- LDS images -------------------------------------------------------------------------------
-// direct image: [128 rows][64 k], 128-B rows, 16-B chunk c of row r stored at chunk c ^ (r & 7)
-__device__ __forceinline__ int off_direct(int row, int ch) { return row * 64 + ((ch ^ (row & 7)) << 3); }
-// transposed-read image: [64 k-rows][128 cols], 256-B rows, chunk c of row r at c ^ (((r&3)<<2)|((r>>2)&3))
-__device__ __forceinline__ int swz_tr(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int off_tr(int krow, int ch) { return krow * 128 + ((ch ^ swz_tr(krow)) << 3); }
-
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-__device__ __forceinline__ bf16x8 frag_direct(const __bf16* img, int row, int kchunk) {
-  return *reinterpret_cast<const bf16x8*>(img + off_direct(row, kchunk));
-}
-// fragment for 16 consecutive columns starting at col0 (multiple of 16), k rows kr0 + 8*(lane>>4) + 0..7
-__device__ __forceinline__ bf16x8 frag_tr(const __bf16* img, int col0, int kr0, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int ch = (col0 >> 3) + (p >> 1);
-  const int r0 = kr0 + 8 * g + q;
-  const __bf16* a0 = img + off_tr(r0, ch) + 4 * (p & 1);
-  const __bf16* a1 = img + off_tr(r0 + 4, ch) + 4 * (p & 1);
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a0);
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a1);
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
 
 // ---- global -> register staging --------------------------------------------------------------
 // direct operand: rows = output index (clamped), k contiguous
@@ -500,7 +474,6 @@ int launch(const GemmArgs& g, hipStream_t s) {
 // the matrix cores.  WM x WN waves, each MT x NT MFMA tiles.
 // =================================================================================================
 typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 // transposed-read image [64 k-rows][COLS]: XOR applied to the 16-B chunk index of row r.  Derived from the
 // ds_read_b64_tr_b16 bank rule (64 banks x 4 B, conflicts counted per 32-lane half = rows r..r+3 and r+8..r+11):
@@ -844,41 +817,9 @@ int launch_fast(GemmArgs g, hipStream_t s) {
 // =================================================================================================
 // Pipelined path ("k_gemm_pipe"): same tiles / LDS images / DMA as k_gemm_fast, but the fragment reads are
 // software pipelined BY HAND one k-step ahead of the MFMAs that consume them, and the transposed reads are
-// issued through inline asm.  Reason (measured): while an LDS-DMA is in flight hipcc puts `s_waitcnt vmcnt(0)`
-// in front of every __builtin ds_read_tr16_b64 (it cannot prove the DMA does not alias the read), which
-// serialises load and compute for the dgrad / wgrad layouts (wgrad fc1: 181 us = 112 us DMA-only + 125 us
-// compute-only with almost no overlap).  An asm read is invisible to that bookkeeping; its completion is waited
-// for explicitly (`s_waitcnt lgkmcnt(0)` + sched_barrier, cdna_hip_programming.md section 5.7 rule 18).
+// issued through inline asm (tile.h asm_read_*: the builtin would drain vmcnt(0) while an LDS-DMA is in flight); their
+// completion is waited for explicitly (lds_reads_done(), cdna_hip_programming.md section 5.7 rule 18).
 // =================================================================================================
-__device__ __forceinline__ unsigned lds_addr(const __bf16* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)(const void*)p;
-}
-__device__ __forceinline__ bf16x4 asm_read_tr(unsigned addr) {
-  bf16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-__device__ __forceinline__ bf16x8 asm_read_b128(unsigned addr) {
-  bf16x8 r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ bf16x4 asm_read_tr_off(unsigned addr) {
-  bf16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ bf16x8 asm_read_b128_off(unsigned addr) {
-  bf16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 // Where the memory operations of a segment sit among its NM MFMAs.  They used to be spread evenly up to the LAST MFMA, so the
 // `s_waitcnt lgkmcnt(0)` that closes the segment exposed one full LDS latency per k-step on BOTH waves of a SIMD at once (the two
 // run the same code from the same barrier: neither has MFMAs left to cover the other).  Now the operations are packed into the
@@ -895,10 +836,6 @@ constexpr int op_span(int nops, int nm) {
   return span < 1 ? 1 : span;
 }
 constexpr int op_cut(int i, int nops, int nm) { return i >= op_span(nops, nm) ? nops : i * nops / op_span(nops, nm); }
-__device__ __forceinline__ void lds_reads_done() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // SCHED 1 ("interleaved"): the same pipeline, but the LDS-DMA issues and fragment reads of a segment are pinned BETWEEN
 // the MFMAs they overlap with (one MFMA, then 1-2 memory instructions, sched_barrier), so their issue slots hide under

@@ -38,9 +38,6 @@ __device__ __forceinline__ void load_row_f32(const float* __restrict__ p, int D4
 // scalar descriptor + one lane offset + immediates.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 struct RowRaw { bf16x4 v[NCH]; };     // a bf16 row as loaded (converted where it is used: half the registers while in flight)
 __device__ __forceinline__ void load_raw_bf16(const __bf16* __restrict__ p, int D4, int lane, RowRaw& r) {
 #pragma unroll

@@ -131,14 +131,6 @@ __device__ __forceinline__ float ema_one(float e, float p, const AdamArgs& a) {
   return a.ema_w * p + a.ema_decay * e;
 }
 
-__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {      // OCP e4m3fn, RNE, saturating (as csrc/fp8.hip)
-  const float mx = 448.0f;
-  int r = 0;
-  r = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a, -mx), mx), fminf(fmaxf(b, -mx), mx), r, false);
-  r = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(c, -mx), mx), fminf(fmaxf(d, -mx), mx), r, true);
-  return (uint32_t)r;
-}
-
 // w8 / w8_scale (optional, config 5): the e4m3 shadow of the NEW p, quantised with the device scalar *w8_scale -- the range is one
 // weight tensor (+ its bias, whose e4m3 bytes nobody reads), so the re-quantisation pass over the masters disappears
 // The sweep touches every word of its arenas exactly once, most of it beside the next forward pass: nontemporal (streaming) accesses keep
@@ -179,7 +171,7 @@ __global__ __launch_bounds__(TPB) void k_masked_clip_adam(float* __restrict__ p,
       bf16x4 b = {f2bf(pp.x), f2bf(pp.y), f2bf(pp.z), f2bf(pp.w)};
       reinterpret_cast<bf16x4*>(wbf)[i] = b;
     }
-    if (w8) reinterpret_cast<uint32_t*>(w8)[i] = pack4_e4m3(pp.x * s8, pp.y * s8, pp.z * s8, pp.w * s8);
+    if (w8) reinterpret_cast<uint32_t*>(w8)[i] = pack_e4m3(pp.x * s8, pp.y * s8, pp.z * s8, pp.w * s8);
     if (a.ema_mode) {
       float4 ee = LD4(ema, i);
       ee.x = ema_one(ee.x, pp.x, a); ee.y = ema_one(ee.y, pp.y, a);

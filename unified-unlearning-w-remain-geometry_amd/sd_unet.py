@@ -6,7 +6,7 @@ context)``, identical ``state_dict()`` keys / shapes / order (checked against or
 to the imported reference), so a CompVis checkpoint's ``model.diffusion_model.*`` entries load unchanged and
 sfron.export.compvis_unet_to_diffusers re-keys them for UNet2DConditionModel.
 
-Blocks (all on the kernels of csrc/conv.hip, no autograd inside -- the tape machinery of sfron.unet):
+Blocks (all on the kernels of csrc/conv.hip, groupnorm.hip and rows.hip, no autograd inside -- the tape machinery of sfron.unet):
   ResBlock (openaimodel.py:177-288)            GroupNorm32(eps 1e-5)+SiLU -> conv3x3 (+ emb projection) -> GroupNorm32+SiLU -> conv3x3
   SpatialTransformer (attention.py:253-303)    GroupNorm(eps 1e-6) -> 1x1 proj_in -> BasicTransformerBlock -> 1x1 proj_out -> + x
   BasicTransformerBlock (:196-250)             LN -> self-attention + x;  LN -> cross-attention(context) + x;  LN -> GEGLU FF + x

@@ -1,4 +1,4 @@
-"""The DDPM conditional U-Net (BASELINE config 0: CIFAR-10 class forgetting) over the HIP kernels of csrc/conv.hip.
+"""The DDPM conditional U-Net (BASELINE config 0: CIFAR-10 class forgetting) over the HIP kernels of csrc/conv.hip, groupnorm.hip and rows.hip.
 
 Mirrors /root/reference/DDPM/models/diffusion.py:195-413 ``Conditional_Model``: same constructor (a config object with
 ``model`` / ``data`` / ``diffusion`` sections, or the same fields as keywords), ``forward(x, t, c, mode, **kwargs)`` with

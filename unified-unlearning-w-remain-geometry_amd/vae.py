@@ -1,4 +1,4 @@
-"""The KL-f8 VAE encoder (image -> posterior moments -> latent) over the HIP kernels of csrc/conv.hip / embed.hip, forward only.
+"""The KL-f8 VAE encoder (image -> posterior moments -> latent) over the HIP kernels of csrc/conv.hip / groupnorm.hip / rows.hip / embed.hip, forward only.
 
 Restates SD/ldm/modules/diffusionmodules/model.py ``Encoder`` (conv_in, per level ``num_res_blocks`` ResnetBlocks [+ AttnBlocks] and a
 (0,1,0,1)-padded stride-2 Downsample, mid ResnetBlock / AttnBlock / ResnetBlock, GroupNorm + swish + conv_out) followed by the
