@@ -167,6 +167,27 @@ int sfron_ddim_cfg_step(const float* x, const float* eps_uncond, const float* ep
                         float sqrt_one_minus_at, float sqrt_at, float sqrt_a_prev, float dir_coef, float sigma, float* x_prev, float* pred_x0,
                         void* stream);
 
+/* ------------------------------------------------------------------ ldm PLMS sampler (plms.hip)
+ * classifier-free guidance + the pseudo linear multistep combination + the eta = 0 update of SD/ldm/models/diffusion/plms.py:311-312,
+ * 349-380 in one pass over n elements; fp32, every step one IEEE operation in the reference's left-to-right order:
+ *   e  = eps_uncond + guidance*(eps_cond - eps_uncond)   (eps_cond NULL: e = eps_uncond);   e_out[i] = e when e_out is given
+ *   e' = e | (3e - old1)/2 | (23e - 16 old1 + 5 old2)/12 | (55e - 59 old1 + 37 old2 - 9 old3)/24 | (old1 + e)/2   by `order`
+ *        (true divisions; MEAN is the second half of the first step: old1 = that step's e_t, e = e_t_next)
+ *   pred_x0 = (x - sqrt_one_minus_at*e')/sqrt_at;   x_prev = sqrt_a_prev*pred_x0 + dir_coef*e'
+ * pred_x0 and e_out may be NULL.  x_prev may be x, and e_out may be the oldest history buffer the call reads (a three-slot ring is
+ * overwritten in place): an element is read before it is written, by the same thread.  SFRON_ERR_ARG before any launch for a NULL x,
+ * eps_uncond or x_prev, n <= 0, sqrt_at == 0, an unknown order, a NULL history pointer the order reads, a guidance that is not finite. */
+enum { SFRON_PLMS_ORDER1 = 0, SFRON_PLMS_ORDER2 = 1, SFRON_PLMS_ORDER3 = 2, SFRON_PLMS_ORDER4 = 3, SFRON_PLMS_MEAN = 4 };
+int sfron_plms_cfg_step(const float* x, const float* eps_uncond, const float* eps_cond, const float* old1, const float* old2,
+                        const float* old3, int order, int64_t n, float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_a_prev,
+                        float dir_coef, float* e_out, float* x_prev, float* pred_x0, void* stream);
+/* the inpainting blend of plms.py:228-233 in one launch: orig = sqrt_ac*x0 + sqrt_one_minus_ac*noise (q_sample at the step's timestep);
+ * out = orig*m + (1 - m)*img.  img, x0, noise, out fp32 [B][C][hw]; m from a mask [mask_b][mask_c][hw] with mask_b 1 or B and mask_c 1
+ * or C (the broadcasts of a [B,1,H,W] or [1,1,H,W] mask).  out may be img.  Any other extent, a NULL pointer or a size <= 0:
+ * SFRON_ERR_ARG. */
+int sfron_inpaint_blend(const float* img, const float* x0, const float* noise, const float* mask, int B, int C, int64_t hw, int mask_b,
+                        int mask_c, float sqrt_ac, float sqrt_one_minus_ac, float* out, void* stream);
+
 /* ------------------------------------------------------------------ bf16 MFMA GEMM (gemm.hip)
  * C[M,N] = alpha * op(A)[M,K] · op(B)[K,N] (+ bias[N]) with a fused epilogue; fp32 accumulation.
  *   a_transposed = 0: A is [M][K] row-major (lda), contraction contiguous      (activations, forward / dgrad)

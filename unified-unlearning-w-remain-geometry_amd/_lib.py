@@ -330,6 +330,11 @@ _PROTOS.update({           # csrc/classify.hip: the ResNet evaluators
     "sfron_pool_fc": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _S]),
     "sfron_classify_metrics": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _S]),
 })
+_PROTOS.update({           # csrc/plms.hip: the ldm PLMS sampler
+    "sfron_plms_cfg_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _S]),
+    "sfron_inpaint_blend": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, c_float, c_float, _P, _S]),
+})
+PLMS_ORDER1, PLMS_ORDER2, PLMS_ORDER3, PLMS_ORDER4, PLMS_MEAN = range(5)       # include/sfron.h SFRON_PLMS_*
 ERR_ARG = 1001                  # SFRON_ERR_ARG
 ERR_UNSUPPORTED = 1002         # SFRON_ERR_UNSUPPORTED (csrc/common.h)
 

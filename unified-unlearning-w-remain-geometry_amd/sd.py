@@ -105,6 +105,10 @@ class LatentDiffusion:
     betas = property(lambda self: self.schedule.betas)
     alphas_cumprod = property(lambda self: self.schedule.alphas_cumprod)
     alphas_cumprod_prev = property(lambda self: self.schedule.alphas_cumprod_prev)
+    # q_sample's two fp32 tables (ddpm.py:190-191: fp64 square roots rounded once; columns 0 and 1 of the packed table), read by the
+    # inpainting loop of sfron.plms.PLMSSampler
+    sqrt_alphas_cumprod = property(lambda self: self.schedule.tab[:, 0])
+    sqrt_one_minus_alphas_cumprod = property(lambda self: self.schedule.tab[:, 1])
 
     def train(self, mode=True):
         self.training = bool(mode)
@@ -360,7 +364,8 @@ def sample_model(model, sampler, c, h, w, ddim_steps, scale, ddim_eta, start_cod
                  till_T=None, verbose=True):
     """SD/train-scripts/train-esd.py:43-84: DDIM-sample ``n_samples`` latents of an h x w image under the conditioning ``c`` with
     guidance ``scale`` (the empty prompt is encoded through ``model.get_learned_conditioning`` when scale != 1).  Returns the latents,
-    or (latents, intermediates) when ``log_every_t`` is given.  ``sampler``: a sfron.ddim.DDIMSampler over ``model``."""
+    or (latents, intermediates) when ``log_every_t`` is given.  ``sampler``: a sfron.ddim.DDIMSampler or a sfron.plms.PLMSSampler (whole
+    trajectories only, eta 0) over ``model``."""
     uc = None
     if scale != 1.0:
         uc = model.get_learned_conditioning(n_samples * [""])
