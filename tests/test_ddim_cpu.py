@@ -98,6 +98,43 @@ def test_sampler_refuses_cpu_model_outputs():
         ddim.DDIMSampler(m).sample(S=4, batch_size=1, shape=(4, 8, 8), conditioning=torch.zeros(1, 5, 24), x_T=torch.zeros(1, 4, 8, 8))
 
 
+def test_chunked_runs_slice_their_operands():
+    """the DDIM twin of test_plms_cpu's test of the same name: both samplers run their chunks through one driver"""
+    from sfron import ddim
+    s = ddim.DDIMSampler(host_model())
+    s.chunk_size = lambda batch_size, shape: 2
+    B = 5
+    g = torch.Generator().manual_seed(1)
+    x_T, cond, uc = torch.randn(B, 4, 8, 8, generator=g), torch.randn(B, 5, 24, generator=g), torch.randn(B, 5, 24, generator=g)
+    noise = torch.randn(4, B, 4, 8, 8, generator=g)
+    seen = []
+
+    def ddim_sampling(cond, shape, **kw):
+        seen.append(dict(cond=cond, shape=shape, **kw))
+        return kw["x_T"] + 1, {"x_inter": [kw["x_T"], kw["x_T"] + 1], "pred_x0": [kw["x_T"], kw["x_T"] - 1]}
+    s.ddim_sampling = ddim_sampling
+    smp, inter = s.sample(S=4, batch_size=B, shape=(4, 8, 8), conditioning=cond, unconditional_conditioning=uc, x_T=x_T, eta=0.5,
+                          step_noise=noise, unconditional_guidance_scale=2.0, log_every_t=1, temperature=0.7, t_start=3, till_T=1,
+                          verbose=False)
+    assert len(s.ddim_timesteps) == 4 and np.all(np.asarray(s.ddim_sigmas, dtype=np.float64)[1:] > 0)          # an eta > 0 schedule
+    assert [c["shape"] for c in seen] == [(2, 4, 8, 8), (2, 4, 8, 8), (1, 4, 8, 8)]
+    for c, (lo, hi) in zip(seen, ((0, 2), (2, 4), (4, 5))):
+        assert torch.equal(c["cond"], cond[lo:hi]) and torch.equal(c["unconditional_conditioning"], uc[lo:hi])
+        assert torch.equal(c["x_T"], x_T[lo:hi])
+        for k in range(4):
+            assert torch.equal(c["step_noise"][k], noise[k][lo:hi])
+        assert c["t_start"] == 3 and c["till_T"] == 1 and c["temperature"] == 0.7 and c["log_every_t"] == 1
+        assert c["unconditional_guidance_scale"] == 2.0
+    assert torch.equal(smp, x_T + 1)
+    assert len(inter["x_inter"]) == len(inter["pred_x0"]) == 2
+    assert torch.equal(inter["x_inter"][0], x_T) and torch.equal(inter["x_inter"][1], x_T + 1)
+    assert torch.equal(inter["pred_x0"][0], x_T) and torch.equal(inter["pred_x0"][1], x_T - 1)
+    # nothing is sliced that is not there
+    seen.clear()
+    s.sample(S=4, batch_size=B, shape=(4, 8, 8), conditioning=cond, x_T=x_T, verbose=False)
+    assert len(seen) == 3 and all(c["step_noise"] is None and c["unconditional_conditioning"] is None for c in seen)
+
+
 def test_generate_images_file_names_and_seeds(tmp_path, monkeypatch):
     from sfron import sd
     csv_path = tmp_path / "prompts.csv"

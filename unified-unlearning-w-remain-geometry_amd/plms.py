@@ -3,11 +3,12 @@
 included.  It is what CompVis ``txt2img`` samples with by default (50 steps at fourth order), and it drops into ``sd.sample_model`` and
 ``sd.generate_images(..., sampler=PLMSSampler(model))``.
 
-What runs where: the schedule tables, the batch chunking and the once-per-call context preparation are the host helpers of sfron.ddim, and
-the step scalars follow the fp32 rule of its ``step_coefficients`` with every square root correctly rounded (see ``_sqrt32``).  A step is
-ONE UNet call at batch 2B (unconditional rows first) and ONE launch of sfron_plms_cfg_step, which reads the two halves of the UNet's
-output in place, mixes them, forms the multistep combination with the (up to) three earlier predictions and applies the eta = 0 update.  The first step has no history: two UNet calls and two launches (ORDER1 keeping e_t, then MEAN), so S steps
-cost S + 1 UNet calls.  The history lives in three device buffers allocated once per call; from the fourth step on the new prediction
+What runs where: the schedule tables, the batch chunking and the once-per-call context preparation are sfron.ldm_sampler's, shared with
+the DDIM sampler, and the step scalars follow the fp32 rule of DDIMSampler's ``step_coefficients`` with every square root correctly
+rounded (see ``_sqrt32``).  A step is ONE UNet call at batch 2B (unconditional rows first) and ONE launch of sfron_plms_cfg_step, which
+reads the two halves of the UNet's output in place, mixes them, forms the multistep combination with the (up to) three earlier
+predictions and applies the eta = 0 update.  The first step has no history: two UNet calls and two launches (ORDER1 keeping e_t, then
+MEAN), so S steps cost S + 1 UNet calls.  The history lives in three device buffers allocated once per call; from the fourth step on the new prediction
 overwrites the oldest one in the launch that read it.  With ``mask`` / ``x0`` one launch of sfron_inpaint_blend in front of each step's
 model call forms ``q_sample(x0, ts) * mask + (1 - mask) * img``.
 
@@ -25,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .ddim import DDIMSampler, _SliceNoise, make_ddim_sampling_parameters, make_ddim_timesteps
+from .ldm_sampler import LDMSampler
 
 _ORDERS = (_lib.PLMS_ORDER1, _lib.PLMS_ORDER2, _lib.PLMS_ORDER3, _lib.PLMS_ORDER4)
 
@@ -40,41 +41,18 @@ def _sqrt32(v):
     return float(np.float32(math.sqrt(float(v))))
 
 
-class PLMSSampler(object):
-    def __init__(self, model, schedule="linear", fused_wide_attn=False, **kwargs):
-        """fused_wide_attn: as in DDIMSampler -- for the duration of a sampling call the native UNet runs its wide-head self-attention on
-        the fused kernels of csrc/wattn.hip; off by default."""
-        super().__init__()
-        self.model = model
-        self.fused_wide_attn = bool(fused_wide_attn)
-        self.ddpm_num_timesteps = model.num_timesteps
-        self.schedule = schedule
-
-    # the host helpers of the DDIM sampler, as they are: the native-UNet lookup, the conditioning tensor of a dict, the once-per-call
-    # context (fused_cross_attention / fused_wide_self_attention set and restored), the 2 GiB batch chunking
-    _unet = DDIMSampler._unet
-    _cond_tensor = staticmethod(DDIMSampler._cond_tensor)
-    _conditioning = DDIMSampler._conditioning
-    chunk_size = DDIMSampler.chunk_size
-    register_buffer = DDIMSampler.register_buffer
+class PLMSSampler(LDMSampler):
+    REFUSED = dict(score_corrector=None, quantize_x0=False, quantize_denoised=False, dynamic_threshold=None, noise_dropout=0.0,
+                   ddim_use_original_steps=False, use_original_steps=False, t_start=-1, till_T=None)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         if ddim_eta != 0:
             raise ValueError("ddim_eta must be 0 for PLMS")
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps)
-        alphas_cumprod = self.model.alphas_cumprod
-        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
-        to_torch = lambda x: torch.as_tensor(x).clone().detach().to(torch.float32).to(self.model.device)
-        ac = alphas_cumprod.cpu()
-        self.register_buffer("betas", to_torch(self.model.betas))
-        self.register_buffer("alphas_cumprod", to_torch(alphas_cumprod))
-        self.register_buffer("alphas_cumprod_prev", to_torch(self.model.alphas_cumprod_prev))
-        self.register_buffer("sqrt_alphas_cumprod", to_torch(ac.sqrt()))
-        self.register_buffer("sqrt_one_minus_alphas_cumprod", to_torch((1.0 - ac).sqrt()))
-        sigmas, alphas, alphas_prev = make_ddim_sampling_parameters(ac, self.ddim_timesteps, ddim_eta)
-        # host-side tables (fp32 tensor / float64 array as the reference leaves them): step_coefficients reads one entry per step
-        self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sigmas, alphas, alphas_prev
-        self.ddim_sqrt_one_minus_alphas = torch.tensor([_sqrt32(v) for v in 1.0 - alphas], dtype=torch.float32)
+        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
+
+    @staticmethod
+    def _sqrt_one_minus(alphas):
+        return torch.tensor([_sqrt32(v) for v in 1.0 - alphas], dtype=torch.float32)
 
     def step_coefficients(self, index):
         """The rule of DDIMSampler.step_coefficients -- the five fp32 scalars of step ``index`` as the reference forms them by fp32 tensor
@@ -86,66 +64,32 @@ class PLMSSampler(object):
         assert rest.dtype == np.float32
         return float(self.ddim_sqrt_one_minus_alphas[index]), _sqrt32(a_t), _sqrt32(a_prev), _sqrt32(rest), float(sigma)
 
-    # ------------------------------------------------------------------------------------------------ guards
-    @staticmethod
-    def _refuse(**kw):
-        for name, (value, unset) in kw.items():
-            bad = value is not None if unset is None else value != unset
-            if bad:
-                raise NotImplementedError(f"PLMSSampler: `{name}` is not built (DESIGN.md section 7)")
-
     # ------------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None, dynamic_threshold=None,
                t_start=-1, till_T=None, verbose_iter=False, inpaint_noise=None, **kwargs):
-        self._refuse(score_corrector=(score_corrector, None), quantize_x0=(bool(quantize_x0), False),
-                     dynamic_threshold=(dynamic_threshold, None), noise_dropout=(float(noise_dropout), 0.0),
-                     ddim_use_original_steps=(bool(kwargs.get("ddim_use_original_steps", False)), False),
-                     t_start=(t_start, -1), till_T=(till_T, None))
-        if conditioning is not None:
-            cbs = self._cond_tensor(conditioning).shape[0]
-            if cbs != batch_size:
-                print(f"Warning: Got {cbs} conditionings but batch-size is {batch_size}")
+        self._refuse(dict(locals(), ddim_use_original_steps=kwargs.get("ddim_use_original_steps", False)))
+        self._warn_batch(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        C, H, W = shape
+        sliced = dict(x_T=x_T, unconditional_conditioning=unconditional_conditioning, x0=x0)
         kw = dict(callback=callback, img_callback=img_callback, temperature=temperature, log_every_t=log_every_t,
                   unconditional_guidance_scale=unconditional_guidance_scale)
-        n = self.chunk_size(batch_size, shape)
-        if n >= batch_size:
-            return self.plms_sampling(conditioning, (batch_size, C, H, W), x_T=x_T, unconditional_conditioning=unconditional_conditioning,
-                                      mask=mask, x0=x0, inpaint_noise=inpaint_noise, **kw)
-        # chunks of the batch, as DDIMSampler.sample runs them: every operand at batch 2 n stays under 2 GiB
-        cut = lambda v, lo, hi: None if v is None else self._cond_tensor(v)[lo:hi]
-        cut_mask = lambda lo, hi: mask if mask is None or mask.shape[0] == 1 else mask[lo:hi]
-        outs = []
-        for lo in range(0, batch_size, n):
-            hi = min(batch_size, lo + n)
-            sn = None if inpaint_noise is None else _SliceNoise(inpaint_noise, lo, hi)
-            outs.append(self.plms_sampling(cut(conditioning, lo, hi), (hi - lo, C, H, W), x_T=cut(x_T, lo, hi),
-                                           unconditional_conditioning=cut(unconditional_conditioning, lo, hi), mask=cut_mask(lo, hi),
-                                           x0=cut(x0, lo, hi), inpaint_noise=sn, **kw))
-        inter = {k: [torch.cat(parts) for parts in zip(*(o[1][k] for o in outs))] for k in outs[0][1]}
-        return torch.cat([o[0] for o in outs]), inter
+        if mask is None or mask.shape[0] == 1:          # a mask of batch extent 1 serves every chunk whole
+            kw["mask"] = mask
+        else:
+            sliced["mask"] = mask
+        return self._chunked(self.plms_sampling, conditioning, batch_size, shape, sliced, dict(inpaint_noise=inpaint_noise), **kw)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None, quantize_denoised=False,
                       mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, dynamic_threshold=None,
                       inpaint_noise=None):
-        self._refuse(score_corrector=(score_corrector, None), quantize_x0=(bool(quantize_denoised), False),
-                     dynamic_threshold=(dynamic_threshold, None), noise_dropout=(float(noise_dropout), 0.0),
-                     ddim_use_original_steps=(bool(ddim_use_original_steps), False))
-        device = self.model.betas.device
+        self._refuse(locals())
+        device, img, timesteps, intermediates = self._begin(shape, x_T, timesteps)
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
-        if timesteps is None:
-            timesteps = self.ddim_timesteps
-        else:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
         if mask is not None:
@@ -174,9 +118,7 @@ class PLMSSampler(object):
                     callback(i)
                 if img_callback:
                     img_callback(pred_x0, i)
-                if index % log_every_t == 0 or index == total_steps - 1:
-                    intermediates["x_inter"].append(img)
-                    intermediates["pred_x0"].append(pred_x0)
+                self._keep(intermediates, index, total_steps, log_every_t, img, pred_x0)
         return img, intermediates
 
     def _blend(self, img, x0, noise, mask, sqrt_ac, sqrt_one_minus_ac):
@@ -198,10 +140,7 @@ class PLMSSampler(object):
     def _update(self, x, out, guided, old, order, guidance, coef, e_out, want_pred=True):
         """One launch of sfron_plms_cfg_step -> (x_prev, pred_x0).  out: the model's output, [2B] rows (unconditional first) when guided;
         old: the history tensors the order reads, newest first; e_out: where the guided prediction is kept (None: not kept)."""
-        if not out.is_cuda:
-            raise _lib.SfronError("sfron ops need GPU tensors (no CPU fallback)")
-        eu = out.data_ptr()
-        ec = eu + out.element_size() * (out.numel() // 2) if guided else None
+        eu, ec = self._halves(out, guided)
         o = [ptr(t) for t in old] + [None] * (3 - len(old))
         s1, s2, s3, dr, _ = coef
         x_prev = torch.empty_like(x)
@@ -217,21 +156,11 @@ class PLMSSampler(object):
         """-> (x_prev, pred_x0, e_t).  old_eps: the earlier guided predictions, oldest first (the last three are read).  _ring: the
         sampling loop's three history buffers; with them e_t is written into the free slot, or over the oldest entry once three are held
         (the loop drops that entry next).  Without, e_t is a new tensor and old_eps is only read."""
-        self._refuse(use_original_steps=(bool(use_original_steps), False), quantize_x0=(bool(quantize_denoised), False),
-                     noise_dropout=(float(noise_dropout), 0.0), score_corrector=(score_corrector, None),
-                     dynamic_threshold=(dynamic_threshold, None))
+        self._refuse(locals())
         x = x.contiguous().float()
         old_eps = [] if old_eps is None else old_eps
         guidance = unconditional_guidance_scale
-        guided = not (unconditional_conditioning is None or guidance == 1.0)
-        if _c_in is None:
-            _c_in = torch.cat([self._cond_tensor(unconditional_conditioning), self._cond_tensor(c)]) if guided else self._cond_tensor(c)
-
-        def model_output(x, t):   # one call at batch 2 B, unconditional rows first; the update reads the two halves where they are
-            if guided:
-                return self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), _c_in).contiguous().float()
-            return self.model.apply_model(x, t, _c_in).contiguous().float()
-
+        guided, _c_in = self._guidance(c, unconditional_conditioning, guidance, _c_in)
         coef = self.step_coefficients(index)
         k = min(len(old_eps), 3)
         old = [v.contiguous().float() for v in reversed(old_eps[len(old_eps) - k:])]          # newest first: old1, old2, old3
@@ -239,12 +168,12 @@ class PLMSSampler(object):
             e_t = torch.empty_like(x)
         else:
             e_t = old_eps[-3] if k == 3 else _ring[k]
-        out = model_output(x, t)
+        out = self._model_output(x, t, _c_in, guided)
         if k > 0:
             x_prev, pred_x0 = self._update(x, out, guided, old, _ORDERS[k], guidance, coef, e_t)
             return x_prev, pred_x0, e_t
         # no history: the pseudo improved Euler step -- a plain update to t_next, a second model call there, the mean of the two predictions
         x_mid, _ = self._update(x, out, guided, [], _lib.PLMS_ORDER1, guidance, coef, e_t, want_pred=False)
-        out = model_output(x_mid, t_next)
+        out = self._model_output(x_mid, t_next, _c_in, guided)
         x_prev, pred_x0 = self._update(x, out, guided, [e_t], _lib.PLMS_MEAN, guidance, coef, None)
         return x_prev, pred_x0, e_t

@@ -12,8 +12,8 @@ they feed a product, in a few workspaces reused across calls, on the current str
 The stem is a patch matrix (sfron_image_u8_patches7 / sfron_nchw_patches7) times the [64][k_pad] weights on the plain GEMM; every other
 convolution is sfron_conv_fwd (3x3 and 1x1, stride 1 and 2); the head is sfron_pool_fc in fp32.
 
-Chunk invariant (as vae.py): the library refuses an operand of 2 GiB or more, so a batch runs in chunks of samples whose largest operand
-stays under ``max_chunk_bytes``; every launch asserts its operands are below 2 GiB.
+Chunk invariant (forward_net.py, as vae.py): the library refuses an operand of 2 GiB or more, so a batch runs in chunks of samples whose
+largest operand stays under ``max_chunk_bytes``; every launch asserts its operands are below 2 GiB.
 """
 import ctypes
 from collections import OrderedDict
@@ -22,16 +22,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import check, lib as _L, ptr, stream_ptr
+from .forward_net import ForwardNet, guard
 
 BN_EPS = 1e-5
 STEM_K = 147                 # 7 * 7 * 3 live columns of the stem's patch matrix
 STEM_K_PAD = 152             # ... padded to a multiple of 8
-_LIMIT = 1 << 31
-
-
-def _L():
-    return _lib.lib()
 
 
 class BasicBlock:
@@ -114,28 +110,18 @@ def resnet_flops(block, layers, num_classes, H, W):
     return total + 2.0 * specs["fc.weight"][0] * specs["fc.weight"][1]
 
 
-def _guard(*tensors):
-    for t in tensors:
-        if t is not None and not isinstance(t, int):
-            nb = t.numel() * t.element_size()
-            assert nb < _LIMIT, f"operand of {nb} bytes: a launch may not read or write 2 GiB or more (chunk the batch)"
-
-
-class ResNet:
+class ResNet(ForwardNet):
     """torchvision's ResNet, forward only: ``model(x)`` takes a normalised fp32 [B, 3, H, W] tensor (what the reference's loader hands to
     the model), ``forward_u8(images, mean, std)`` uint8 [B, H, W, 3] bytes that it normalises on the fly.  Both return fp32 logits
     [B, num_classes] on the device."""
 
     def __init__(self, block, layers, num_classes=1000, device="cuda", max_chunk_bytes=1 << 30):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.SfronError("ResNet needs a GPU (no CPU fallback)")
+        super().__init__(device)
         self.block, self.layers, self.num_classes = block, tuple(layers), int(num_classes)
         self.max_chunk_bytes = int(max_chunk_bytes)
         self.specs, self.convs, self.blocks = resnet_plan(block, layers, num_classes)
         self.feat = self.specs["fc.weight"][1]
         self._loaded = None
-        self._ws = {}
         self.training = False
 
     # ---------------------------------------------------------------- torch.nn.Module's surface, as far as inference goes
@@ -180,7 +166,7 @@ class ResNet:
 
         def put(name, t):
             nonlocal off
-            index[name] = (off, tuple(t.shape))
+            index[name] = off
             host.append((off, t.reshape(-1).to(torch.float32)))
             off = (off + t.numel() + 7) // 8 * 8
 
@@ -215,11 +201,8 @@ class ResNet:
             raise _lib.SfronError("ResNet.state_dict: no weights loaded")
         return OrderedDict((n, v.clone()) for n, v in self._loaded.items())
 
-    def _p(self, name):
-        return self.params.data_ptr() + 4 * self.index[name][0]
-
-    def _w(self, name):
-        return self.params_bf16.data_ptr() + 2 * self.index[name][0]
+    def view(self, name):
+        raise NotImplementedError("ResNet.view: the arena holds BatchNorm-folded weights, not the state dict's tensors; use state_dict()")
 
     # ---------------------------------------------------------------- the 2 GiB rule
     def per_sample_bytes(self, H, W):
@@ -236,26 +219,14 @@ class ResNet:
                 big = max(big, h * w * cout * 4)
         return big
 
-    def chunk_size(self, H, W):
-        ps = self.per_sample_bytes(H, W)
-        if ps >= _LIMIT:
-            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB")
-        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
-
-    # ---------------------------------------------------------------- workspaces and launches
-    def _buf(self, key, numel, dtype):
-        t = self._ws.get(key)
-        if t is None or t.numel() < numel:
-            self._ws[key] = t = torch.empty(numel, dtype=dtype, device=self.dev)
-        return t[:numel]
-
+    # ---------------------------------------------------------------- launches
     def _conv(self, i, src, B, h, w, out_key, resid=None):
         """Convolution i (+ folded BatchNorm bias, + fp32 residual) of bf16 rows [B * h * w][c_in] -> fp32 rows, and the output size."""
         from .unet import _conv_desc
         conv, _, cin, cout, k, s, p = self.convs[i]
         ho, wo = _out_size(h, k, s, p), _out_size(w, k, s, p)
         out = self._buf(out_key, B * ho * wo * cout, torch.float32)
-        _guard(src, out, resid)
+        guard(src, out, resid)
         d = _conv_desc(B, h, w, cin, ho, wo, cout, k * k, s, p, 0, 0, bias=self._p(conv + ".b"), resid=resid, out_f32=out, ld_out=cout)
         wt = ptr(self.conv3[conv]) if k == 3 else self._w(conv + ".w")
         check(_L().sfron_conv_fwd(ctypes.byref(d), ptr(src), wt, stream_ptr()), f"conv_fwd({conv})")
@@ -264,7 +235,7 @@ class ResNet:
     def _relu(self, x, rows, C, bf_key, keep_f32):
         """bf16(max(x, 0)) for the next product; with keep_f32 x itself becomes max(x, 0) too (the next block's residual)."""
         y = self._buf(bf_key, rows * C, torch.bfloat16)
-        _guard(x, y)
+        guard(x, y)
         check(_L().sfron_relu_rows(ptr(x), C, rows, C, ptr(y), ptr(x) if keep_f32 else None, stream_ptr()), "relu_rows")
         return y
 
@@ -278,13 +249,13 @@ class ResNet:
             H, W = images.shape[2], images.shape[3]
         h, w = _out_size(H, 7, 2, 3), _out_size(W, 7, 2, 3)
         pat = self._buf("bf_patch", B * h * w * STEM_K_PAD, torch.bfloat16)
-        _guard(src, pat)
+        guard(src, pat)
         if norm is not None:
             check(L.sfron_image_u8_patches7(ptr(src), B, H, W, *norm, STEM_K_PAD, ptr(pat), stream_ptr()), "image_u8_patches7")
         else:
             check(L.sfron_nchw_patches7(ptr(src), B, H, W, STEM_K_PAD, ptr(pat), stream_ptr()), "nchw_patches7")
         stem = self._buf("f_t", B * h * w * 64, torch.float32)
-        _guard(stem)
+        guard(stem)
         bgemm(pat, self._w("conv1.w"), B * h * w, 64, STEM_K_PAD, lda=STEM_K_PAD, ldb=STEM_K_PAD, bias=self._p("conv1.b"), c_f32=stem, ldc=64)
         hp, wp = _out_size(h, 3, 2, 1), _out_size(w, 3, 2, 1)
         xf = self._buf("f_x0", B * hp * wp * 64, torch.float32)

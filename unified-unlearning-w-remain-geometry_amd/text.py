@@ -13,7 +13,7 @@ restated: text that ftfy would change can tokenize differently from an ftfy-equi
 Weights live in one fp32 arena (matrices first, q / k / v of a layer concatenated into one [3D][D] matrix + [3D] bias) and a bf16 shadow
 of the matrix region the products read.  Activations live in workspaces grown on demand and reused by every later call, on the current
 stream.  Operand bound: the products address their operands with 32-bit byte counts, so every launch asserts that no operand reaches 2 GiB
-(vae.py's chunk invariant); at width 768 that is about 350 000 prompts per call, far beyond any batch this is meant for.
+(forward_net.py's rule); at width 768 that is about 350 000 prompts per call, far beyond any batch this is meant for.
 """
 import ctypes
 import json
@@ -26,17 +26,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
-from .vae import _guard
+from ._lib import check, lib as _L, ptr, stream_ptr
+from .forward_net import ForwardNet, guard
 
 BOS, EOS = "<|startoftext|>", "<|endoftext|>"
 LN_EPS = 1e-5
 HEAD_DIM = 64
 MAX_T = 128                   # sfron_attn_causal_fwd
-
-
-def _L():
-    return _lib.lib()
 
 
 # ------------------------------------------------------------------------------------------------ tokenizer
@@ -305,15 +301,13 @@ def load_state_file(path):
 
 
 # ------------------------------------------------------------------------------------------------ the encoder
-class CLIPTextEncoder:
+class CLIPTextEncoder(ForwardNet):
     """prompts -> fp32 [B, 77, D] last_hidden_state on the GPU (FrozenCLIPEmbedder.encode).  ``encode_ids(ids)`` runs the transformer on
     int64 ids [B, T] (T <= 77); ``encode(texts)`` tokenizes first (needs ``tokenizer``); ``__call__`` = encode."""
 
     def __init__(self, vocab_size=49408, max_position=77, width=768, layers=12, heads=None, mlp=3072, tokenizer=None, max_length=77,
                  device="cuda"):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.SfronError("CLIPTextEncoder needs a GPU (no CPU fallback)")
+        super().__init__(device)
         heads = width // HEAD_DIM if heads is None else heads
         if heads * HEAD_DIM != width:
             raise ValueError(f"width {width} with {heads} heads: the attention kernel takes head_dim {HEAD_DIM} only")
@@ -327,7 +321,6 @@ class CLIPTextEncoder:
         self.n_mat = self.index[names[n_mat]]                    # the matrices are the arena's prefix
         self.params = torch.zeros(self.n_total, dtype=torch.float32, device=self.dev)
         self.params_bf16 = torch.zeros(self.n_mat, dtype=torch.bfloat16, device=self.dev)
-        self._ws = {}
 
     # ---------------------------------------------------------------- weights
     @classmethod
@@ -357,25 +350,9 @@ class CLIPTextEncoder:
         check(_L().sfron_cast_bf16(ptr(self.params), ptr(self.params_bf16), self.n_mat, stream_ptr()), "cast_bf16")
         return self
 
-    def view(self, name):
-        n = int(np.prod(self.specs[name]))
-        return self.params[self.index[name]:self.index[name] + n].view(self.specs[name])
-
-    def _p(self, name):
-        return self.params.data_ptr() + 4 * self.index[name]
-
-    def _w(self, name):
-        return self.params_bf16.data_ptr() + 2 * self.index[name]
-
-    def _buf(self, key, numel, dtype):
-        t = self._ws.get(key)
-        if t is None or t.numel() < numel:
-            self._ws[key] = t = torch.empty(numel, dtype=dtype, device=self.dev)
-        return t[:numel]
-
     # ---------------------------------------------------------------- forward
     def _gemm(self, a, w, M, N, K, bias, epi, c_bf16=None, c_f32=None, accumulate=0):
-        _guard(a, c_bf16, c_f32)
+        guard(a, c_bf16, c_f32)
         d = _lib.GemmDesc(A=a.data_ptr(), B=w, M=M, N=N, K=K, lda=K, ldb=K, epilogue=epi, alpha=1.0, bias=bias,
                           c_bf16=c_bf16.data_ptr() if c_bf16 is not None else None, ldc_bf16=N,
                           c_f32=c_f32.data_ptr() if c_f32 is not None else None, ldc_f32=N, tokens=1, accumulate=accumulate)
@@ -384,7 +361,7 @@ class CLIPTextEncoder:
     def _ln(self, x, rows, name):
         y = self._buf("bf_h", rows * self.D, torch.bfloat16)
         mean, rstd = self._buf("ln_mean", rows, torch.float32), self._buf("ln_rstd", rows, torch.float32)
-        _guard(x, y)
+        guard(x, y)
         check(_L().sfron_layernorm_fwd(ptr(x), self._p(name + ".weight"), self._p(name + ".bias"), rows, self.D, LN_EPS, ptr(y), ptr(mean),
                                        ptr(rstd), stream_ptr()), "layernorm_fwd")
         return y
@@ -404,7 +381,7 @@ class CLIPTextEncoder:
         x = self._buf("f_x", rows * D, torch.float32)
         err = self._buf("err", 1, torch.int32)
         err.zero_()
-        _guard(x)
+        guard(x)
         check(_L().sfron_clip_embed(ptr(ids), B, T, self._p("embeddings.token_embedding.weight"), self.vocab,
                                     self._p("embeddings.position_embedding.weight"), D, ptr(x), ptr(err), stream_ptr()), "clip_embed")
         qkv = self._buf("bf_qkv", rows * 3 * D, torch.bfloat16)
@@ -414,7 +391,7 @@ class CLIPTextEncoder:
             L = f"encoder.layers.{i}."
             h = self._ln(x, rows, L + "layer_norm1")
             self._gemm(h, self._w(L + "self_attn.qkv_proj.weight"), rows, 3 * D, D, self._p(L + "self_attn.qkv_proj.bias"), _lib.EPI_BF16, c_bf16=qkv)
-            _guard(qkv, o)
+            guard(qkv, o)
             check(_L().sfron_attn_causal_fwd(ptr(qkv), ptr(o), B, T, self.H, HEAD_DIM, stream_ptr()), "attn_causal_fwd")
             self._gemm(o, self._w(L + "self_attn.out_proj.weight"), rows, D, D, self._p(L + "self_attn.out_proj.bias"), _lib.EPI_F32, c_f32=x,
                        accumulate=1)
@@ -422,7 +399,7 @@ class CLIPTextEncoder:
             self._gemm(h, self._w(L + "mlp.fc1.weight"), rows, F, D, self._p(L + "mlp.fc1.bias"), _lib.EPI_QUICK_GELU, c_bf16=a)
             self._gemm(a, self._w(L + "mlp.fc2.weight"), rows, D, F, self._p(L + "mlp.fc2.bias"), _lib.EPI_F32, c_f32=x, accumulate=1)
         out = torch.empty(B, T, D, dtype=torch.float32, device=self.dev)
-        _guard(out)
+        guard(out)
         check(_L().sfron_layernorm_fwd_f32(ptr(x), self._p("final_layer_norm.weight"), self._p("final_layer_norm.bias"), rows, D, LN_EPS,
                                            ptr(out), stream_ptr()), "layernorm_fwd_f32")
         if check_ids and int(err.item()):

@@ -28,75 +28,70 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import check, lib as _L, ptr, stream_ptr
+from .forward_net import ForwardNet, guard
 from .unet import _conv_desc, _pad8, bgemm
 
 GN_EPS = 1e-6
-_LIMIT = 1 << 31          # bytes: no operand of a launch may reach this (32-bit buffer-resource sizes)
-
-
-def _L():
-    return _lib.lib()
-
-
-def _guard(*tensors):
-    for t in tensors:
-        if t is not None and not isinstance(t, int):
-            nb = t.numel() * t.element_size()
-            assert nb < _LIMIT, f"operand of {nb} bytes: a launch may not read or write 2 GiB or more (chunk the batch)"
 
 
 # ------------------------------------------------------------------------------------------------ structure and weight formats
+# Parameter specs of the blocks both plans are made of, appended to ``dst`` in the modules' registration order; ``res`` also notes its op.
+def _conv_spec(dst, name, o, i, k):
+    dst.extend([(name + ".weight", (o, i, k, k)), (name + ".bias", (o,))])
+
+
+def _gn_spec(dst, name, c):
+    dst.extend([(name + ".weight", (c,)), (name + ".bias", (c,))])
+
+
+def _res_spec(dst, ops, name, cin, cout):
+    _gn_spec(dst, name + ".norm1", cin)
+    _conv_spec(dst, name + ".conv1", cout, cin, 3)
+    _gn_spec(dst, name + ".norm2", cout)
+    _conv_spec(dst, name + ".conv2", cout, cout, 3)
+    if cin != cout:
+        _conv_spec(dst, name + ".nin_shortcut", cout, cin, 1)
+    ops.append(("res", name, cin, cout))
+
+
+def _attn_spec(dst, name, c):
+    _gn_spec(dst, name + ".norm", c)
+    for w in ("q", "k", "v", "proj_out"):
+        _conv_spec(dst, name + "." + w, c, c, 1)
+
+
 def encoder_plan(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, in_channels=3, attn_resolutions=(), resolution=256):
     """(parameter specs in Encoder.named_parameters() order + quant_conv, op list) of the reference Encoder's construction
     (model.py:379-466).  Ops: ("conv_in",), ("res", name, cin, cout), ("attn", name, c), ("down", name, c), ("out", c)."""
     P, ops = [], []
-
-    def conv(name, o, i, k):
-        P.extend([(name + ".weight", (o, i, k, k)), (name + ".bias", (o,))])
-
-    def gn(name, c):
-        P.extend([(name + ".weight", (c,)), (name + ".bias", (c,))])
-
-    def res(name, cin, cout):
-        gn(name + ".norm1", cin); conv(name + ".conv1", cout, cin, 3); gn(name + ".norm2", cout); conv(name + ".conv2", cout, cout, 3)
-        if cin != cout:
-            conv(name + ".nin_shortcut", cout, cin, 1)
-        ops.append(("res", name, cin, cout))
-
-    def attn(name, c):
-        gn(name + ".norm", c)
-        for w in ("q", "k", "v", "proj_out"):
-            conv(name + "." + w, c, c, 1)
-
-    conv("conv_in", ch, in_channels, 3)
+    _conv_spec(P, "conv_in", ch, in_channels, 3)
     ops.append(("conv_in",))
     cur, in_mult, block_in = resolution, (1,) + tuple(ch_mult), ch
     for lvl in range(len(ch_mult)):
         block_in, block_out = ch * in_mult[lvl], ch * ch_mult[lvl]
         attns = []
         for ib in range(num_res_blocks):
-            res(f"down.{lvl}.block.{ib}", block_in, block_out)
+            _res_spec(P, ops, f"down.{lvl}.block.{ib}", block_in, block_out)
             block_in = block_out
             if cur in attn_resolutions:
                 attns.append(f"down.{lvl}.attn.{ib}")
                 ops.append(("attn", attns[-1], block_in))
         for a in attns:                              # the attn ModuleList is registered after the block ModuleList
-            attn(a, block_in)
+            _attn_spec(P, a, block_in)
         if lvl != len(ch_mult) - 1:
-            conv(f"down.{lvl}.downsample.conv", block_in, block_in, 3)
+            _conv_spec(P, f"down.{lvl}.downsample.conv", block_in, block_in, 3)
             ops.append(("down", f"down.{lvl}.downsample.conv", block_in))
             cur //= 2
     # the ModuleList ops above interleave blocks and attentions in execution order; parameters follow registration order
-    res("mid.block_1", block_in, block_in)
-    attn("mid.attn_1", block_in)
+    _res_spec(P, ops, "mid.block_1", block_in, block_in)
+    _attn_spec(P, "mid.attn_1", block_in)
     ops.append(("attn", "mid.attn_1", block_in))
-    res("mid.block_2", block_in, block_in)
-    gn("norm_out", block_in)
-    conv("conv_out", 2 * z_channels, block_in, 3)
+    _res_spec(P, ops, "mid.block_2", block_in, block_in)
+    _gn_spec(P, "norm_out", block_in)
+    _conv_spec(P, "conv_out", 2 * z_channels, block_in, 3)
     ops.append(("out", block_in))
-    conv("quant_conv", 2 * z_channels, 2 * z_channels, 1)
+    _conv_spec(P, "quant_conv", 2 * z_channels, 2 * z_channels, 1)
     return OrderedDict(P), ops
 
 
@@ -166,23 +161,22 @@ def _ldm_name(key):
     raise KeyError(f"unknown diffusers VAE encoder key {key!r}")
 
 
-def canonical_state_dict(sd, specs=None):
-    """Any supported VAE state dict -> {ldm Encoder name (no prefix) | quant_conv.*: fp32 CPU tensor}, shaped as the ldm modules.
-    Formats: ldm AutoencoderKL (encoder.* + quant_conv.*), a CompVis LDM checkpoint (first_stage_model.*, optionally under
-    "state_dict"), diffusers AutoencoderKL (query/key/value/proj_attn or to_q/to_k/to_v/to_out.0 attention names; its Linear [C, C]
-    attention weights become 1x1 convolutions).  Decoder keys are ignored.  ``specs`` (encoder_plan's) checks names and shapes: an
-    incomplete or unknown key set raises and names the keys."""
+def _canonical(sd, specs, side, conv, blocks, mapper):
+    """What canonical_state_dict / canonical_decoder_state_dict do.  side: "encoder" | "decoder", the key prefix and the word in the
+    messages; conv: the AutoencoderKL convolution kept with it; blocks: the diffusers block list that tells diffusers keys apart;
+    mapper(sd) -> the function diffusers key -> ldm name (None: not this side's)."""
     if "state_dict" in sd and isinstance(sd["state_dict"], dict):
         sd = sd["state_dict"]
     if any(k.startswith("first_stage_model.") for k in sd):
         sd = {k[len("first_stage_model."):]: v for k, v in sd.items() if k.startswith("first_stage_model.")}
-    diffusers = any(k.startswith(("encoder.down_blocks.", "encoder.mid_block.", "encoder.conv_norm_out.")) for k in sd)
+    pre = side + "."
+    if any(k.startswith((pre + blocks, pre + "mid_block.", pre + "conv_norm_out.")) for k in sd):
+        name = mapper(sd)
+    else:
+        name = lambda k: k[len(pre):] if k.startswith(pre) else (k if k.startswith(conv + ".") else None)
     out = OrderedDict()
     for k, v in sd.items():
-        if diffusers:
-            n = _ldm_name(k)
-        else:
-            n = k[len("encoder."):] if k.startswith("encoder.") else (k if k.startswith("quant_conv.") else None)
+        n = name(k)
         if n is None:
             continue
         t = torch.as_tensor(v).detach().to("cpu", torch.float32)
@@ -190,12 +184,12 @@ def canonical_state_dict(sd, specs=None):
             t = t.reshape(t.shape[0], t.shape[1], 1, 1)
         out[n] = t
     if not out:
-        raise KeyError(f"not a VAE state dict: no encoder.* / quant_conv.* / first_stage_model.* keys (first keys: {list(sd)[:5]})")
+        raise KeyError(f"not a VAE state dict: no {side}.* / {conv}.* / first_stage_model.* keys (first keys: {list(sd)[:5]})")
     if specs is not None:
         missing = [n for n in specs if n not in out]
         extra = [n for n in out if n not in specs]
         if missing or extra:
-            raise KeyError(f"VAE encoder state dict does not match the configuration: missing {missing[:8]}"
+            raise KeyError(f"VAE {side} state dict does not match the configuration: missing {missing[:8]}"
                            f"{' ...' if len(missing) > 8 else ''}, unexpected {extra[:8]}")
         for n, shp in specs.items():
             if tuple(out[n].shape) != tuple(shp):
@@ -204,63 +198,53 @@ def canonical_state_dict(sd, specs=None):
     return out
 
 
+def canonical_state_dict(sd, specs=None):
+    """Any supported VAE state dict -> {ldm Encoder name (no prefix) | quant_conv.*: fp32 CPU tensor}, shaped as the ldm modules.
+    Formats: ldm AutoencoderKL (encoder.* + quant_conv.*), a CompVis LDM checkpoint (first_stage_model.*, optionally under
+    "state_dict"), diffusers AutoencoderKL (query/key/value/proj_attn or to_q/to_k/to_v/to_out.0 attention names; its Linear [C, C]
+    attention weights become 1x1 convolutions).  Decoder keys are ignored.  ``specs`` (encoder_plan's) checks names and shapes: an
+    incomplete or unknown key set raises and names the keys."""
+    return _canonical(sd, specs, "encoder", "quant_conv", "down_blocks.", lambda sd: _ldm_name)
+
+
 def decoder_plan(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3, attn_resolutions=(), resolution=256):
     """(parameter specs in Decoder.named_parameters() order + post_quant_conv, op list in execution order) of the reference Decoder
     (model.py:496-626) and AutoencoderKL's post_quant_conv (autoencoder.py:385-389).  The up levels run from the top down but are
     registered from level 0 up (``self.up.insert(0, up)``).  Ops: ("conv_in", zc, c), ("res", name, cin, cout), ("attn", name, c),
     ("up", name, c) (nearest x2 + 3x3 conv, model.py:44-57), ("out", c)."""
     P, ops = [], []
-
-    def conv(dst, name, o, i, k):
-        dst.extend([(name + ".weight", (o, i, k, k)), (name + ".bias", (o,))])
-
-    def gn(dst, name, c):
-        dst.extend([(name + ".weight", (c,)), (name + ".bias", (c,))])
-
-    def res(dst, name, cin, cout):
-        gn(dst, name + ".norm1", cin); conv(dst, name + ".conv1", cout, cin, 3); gn(dst, name + ".norm2", cout)
-        conv(dst, name + ".conv2", cout, cout, 3)
-        if cin != cout:
-            conv(dst, name + ".nin_shortcut", cout, cin, 1)
-        ops.append(("res", name, cin, cout))
-
-    def attn(dst, name, c):
-        gn(dst, name + ".norm", c)
-        for w in ("q", "k", "v", "proj_out"):
-            conv(dst, name + "." + w, c, c, 1)
-
     nl = len(ch_mult)
     block_in = ch * ch_mult[nl - 1]
     cur = resolution // 2 ** (nl - 1)
-    conv(P, "conv_in", block_in, z_channels, 3)
+    _conv_spec(P, "conv_in", block_in, z_channels, 3)
     ops.append(("conv_in", z_channels, block_in))
-    res(P, "mid.block_1", block_in, block_in)
-    attn(P, "mid.attn_1", block_in)
+    _res_spec(P, ops, "mid.block_1", block_in, block_in)
+    _attn_spec(P, "mid.attn_1", block_in)
     ops.append(("attn", "mid.attn_1", block_in))
-    res(P, "mid.block_2", block_in, block_in)
+    _res_spec(P, ops, "mid.block_2", block_in, block_in)
     levels = {}
     for lvl in reversed(range(nl)):
         L, attns = [], []
         block_out = ch * ch_mult[lvl]
         for ib in range(num_res_blocks + 1):
-            res(L, f"up.{lvl}.block.{ib}", block_in, block_out)
+            _res_spec(L, ops, f"up.{lvl}.block.{ib}", block_in, block_out)
             block_in = block_out
             if cur in attn_resolutions:
                 attns.append(f"up.{lvl}.attn.{ib}")
                 ops.append(("attn", attns[-1], block_in))
         for a in attns:                              # the attn ModuleList is registered after the block ModuleList
-            attn(L, a, block_in)
+            _attn_spec(L, a, block_in)
         if lvl != 0:
-            conv(L, f"up.{lvl}.upsample.conv", block_in, block_in, 3)
+            _conv_spec(L, f"up.{lvl}.upsample.conv", block_in, block_in, 3)
             ops.append(("up", f"up.{lvl}.upsample.conv", block_in))
             cur *= 2
         levels[lvl] = L
     for lvl in range(nl):                            # registration order: up.0 first
         P.extend(levels[lvl])
-    gn(P, "norm_out", block_in)
-    conv(P, "conv_out", out_ch, block_in, 3)
+    _gn_spec(P, "norm_out", block_in)
+    _conv_spec(P, "conv_out", out_ch, block_in, 3)
     ops.append(("out", block_in))
-    conv(P, "post_quant_conv", z_channels, z_channels, 1)
+    _conv_spec(P, "post_quant_conv", z_channels, z_channels, 1)
     return OrderedDict(P), ops
 
 
@@ -329,39 +313,11 @@ def canonical_decoder_state_dict(sd, specs=None):
     The formats of ``canonical_state_dict`` (ldm AutoencoderKL decoder.* + post_quant_conv.*, CompVis first_stage_model.*, diffusers with
     either attention naming; Linear [C, C] attention weights become 1x1 convolutions).  Encoder keys are ignored.  ``specs``
     (decoder_plan's) checks names and shapes: an incomplete or unknown key set raises and names the keys."""
-    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
-        sd = sd["state_dict"]
-    if any(k.startswith("first_stage_model.") for k in sd):
-        sd = {k[len("first_stage_model."):]: v for k, v in sd.items() if k.startswith("first_stage_model.")}
-    diffusers = any(k.startswith(("decoder.up_blocks.", "decoder.mid_block.", "decoder.conv_norm_out.")) for k in sd)
-    if diffusers:
+    def mapper(sd):
         levels = _levels(specs) if specs is not None else \
             1 + max([int(k.split(".")[2]) for k in sd if k.startswith("decoder.up_blocks.")] or [0])
-    out = OrderedDict()
-    for k, v in sd.items():
-        if diffusers:
-            n = _ldm_decoder_name(k, levels)
-        else:
-            n = k[len("decoder."):] if k.startswith("decoder.") else (k if k.startswith("post_quant_conv.") else None)
-        if n is None:
-            continue
-        t = torch.as_tensor(v).detach().to("cpu", torch.float32)
-        if t.dim() == 2 and ".attn" in n and n.endswith(".weight"):          # diffusers Linear -> 1x1 conv
-            t = t.reshape(t.shape[0], t.shape[1], 1, 1)
-        out[n] = t
-    if not out:
-        raise KeyError(f"not a VAE state dict: no decoder.* / post_quant_conv.* / first_stage_model.* keys (first keys: {list(sd)[:5]})")
-    if specs is not None:
-        missing = [n for n in specs if n not in out]
-        extra = [n for n in out if n not in specs]
-        if missing or extra:
-            raise KeyError(f"VAE decoder state dict does not match the configuration: missing {missing[:8]}"
-                           f"{' ...' if len(missing) > 8 else ''}, unexpected {extra[:8]}")
-        for n, shp in specs.items():
-            if tuple(out[n].shape) != tuple(shp):
-                raise ValueError(f"{n}: shape {tuple(out[n].shape)}, the configuration needs {tuple(shp)}")
-        out = OrderedDict((n, out[n]) for n in specs)
-    return out
+        return lambda k: _ldm_decoder_name(k, levels)
+    return _canonical(sd, specs, "decoder", "post_quant_conv", "up_blocks.", mapper)
 
 
 def load_state_file(path):
@@ -384,7 +340,7 @@ def load_state_file(path):
 
 
 # ------------------------------------------------------------------------------------------------ the encoder
-class _VAENet:
+class _VAENet(ForwardNet):
     """What the encoder and the decoder share: the weight arena (fp32 + bf16 copy, conv_wprep operands), the grown-never-shrunk
     workspaces and the forward blocks over the HIP kernels.  A subclass sets ``specs`` / ``ops`` and calls ``_arena``."""
 
@@ -413,7 +369,6 @@ class _VAENet:
                 co, ci = shp[0], shp[1]
                 self.conv3[n[:-7]] = dict(co=co, ci=ci, cop=_pad8(co), cip=_pad8(ci),
                                           fwd=torch.zeros(_pad8(co) * 9 * _pad8(ci), dtype=torch.bfloat16, device=self.dev))
-        self._ws = {}
         self._zero_bias = {}
 
     # ---------------------------------------------------------------- weights
@@ -445,10 +400,6 @@ class _VAENet:
     def state_dict(self):
         return OrderedDict((n, self.view(n).detach().cpu().clone()) for n in self.specs)
 
-    def view(self, name):
-        n = int(np.prod(self.specs[name]))
-        return self.params[self.index[name]:self.index[name] + n].view(self.specs[name])
-
     def load_state_dict(self, sd):
         can = self._canonical(sd)
         with torch.no_grad():
@@ -464,27 +415,13 @@ class _VAENet:
                 self._zero_bias[base] = b
         return self
 
-    def _p(self, name):
-        return self.params.data_ptr() + 4 * self.index[name]
-
-    def _w(self, name):
-        return self.params_bf16.data_ptr() + 2 * self.index[name]
-
-    # ---------------------------------------------------------------- workspaces
-    def _buf(self, key, numel, dtype):
-        """A view of the first numel elements of workspace `key` (grown, never shrunk; reused by every later call)."""
-        t = self._ws.get(key)
-        if t is None or t.numel() < numel:
-            self._ws[key] = t = torch.empty(numel, dtype=dtype, device=self.dev)
-        return t[:numel]
-
     # ---------------------------------------------------------------- blocks (forward only)
     def _gn(self, x, B, HW, C, name, swish, out_key):
         y = self._buf(out_key, B * HW * C, torch.bfloat16)
         mean = self._buf("gn_mean", B * 32, torch.float32)
         rstd = self._buf("gn_rstd", B * 32, torch.float32)
         ws = self._buf("gn_ws", _L().sfron_groupnorm_scratch_bytes(B, HW, C, 32) // 4 + 4, torch.float32)
-        _guard(x, y)
+        guard(x, y)
         check(_L().sfron_groupnorm_fwd(ptr(x), C, self._p(name + ".weight"), self._p(name + ".bias"), B, HW, C, 32, GN_EPS, int(swish), None, 1.0,
                                        ptr(y), ptr(mean), ptr(rstd), ptr(ws), stream_ptr()), "groupnorm_fwd")
         return y
@@ -494,14 +431,14 @@ class _VAENet:
         out = self._buf(out_key, B * ho * wo * v["cop"], torch.float32).view(B * ho * wo, v["cop"])
         bias = self._zero_bias.get(name)
         bias = self._p(name + ".bias") if bias is None else bias
-        _guard(src, out, resid)
+        guard(src, out, resid)
         d = _conv_desc(B, hs, ws, v["cip"], ho, wo, v["cop"], 9, stride, pad, up, 0, bias=bias, resid=resid, out_f32=out, ld_out=v["cop"])
         check(_L().sfron_conv_fwd(ctypes.byref(d), ptr(src), ptr(v["fwd"]), stream_ptr()), "conv_fwd")
         return out
 
     def _cast(self, x, rows, C, key):
         y = self._buf(key, rows * C, torch.bfloat16)
-        _guard(x, y)
+        guard(x, y)
         check(_L().sfron_cast_rows_bf16(ptr(x), C, rows, C, ptr(y), stream_ptr()), "cast_rows")
         return y
 
@@ -514,7 +451,7 @@ class _VAENet:
         if cin != cout:
             xb = self._cast(x, B * HW, cin, "bf_b")
             sc = self._buf("f_sc", B * HW * cout, torch.float32)
-            _guard(xb, sc)
+            guard(xb, sc)
             bgemm(xb, self._w(name + ".nin_shortcut.weight"), B * HW, cout, cin, lda=cin, ldb=cin, bias=self._p(name + ".nin_shortcut.bias"),
                   c_f32=sc, ldc=cout)
         else:
@@ -526,21 +463,20 @@ class _VAENet:
         T, rows = H * W, B * H * W
         hn = self._gn(x, B, T, C, name + ".norm", False, "bf_a")
         qkv = self._buf("bf_qkv", rows * 3 * C, torch.bfloat16)
-        _guard(hn, qkv)
+        guard(hn, qkv)
         bgemm(hn, self._w(name + ".q.weight"), rows, 3 * C, C, lda=C, ldb=C, bias=self._p(name + ".q.bias"), c_bf16=qkv, ldc=3 * C)
         q, k, v = qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C
         S = self._buf("f_s", B * T * T, torch.float32)
-        _guard(S)
+        guard(S)
         bgemm(q, k, T, T, C, lda=3 * C, ldb=3 * C, batch=B, sa=T * 3 * C, sb=T * 3 * C, sc=T * T, c_f32=S, ldc=T)
         Pm = self._buf("bf_p", B * T * T, torch.bfloat16)
         check(_L().sfron_softmax_fwd(ptr(S), B * T, T, T, float(int(C) ** (-0.5)), ptr(Pm), stream_ptr()), "softmax_fwd")
         O = self._buf("bf_b", rows * C, torch.bfloat16)
         bgemm(Pm, v, T, C, T, lda=T, ldb=3 * C, b_t=True, batch=B, sa=T * T, sb=T * 3 * C, sc=T * C, c_bf16=O, ldc=C)
         out = self._buf(out_key, rows * C, torch.float32)
-        _guard(O, out, x)
+        guard(O, out, x)
         bgemm(O, self._w(name + ".proj_out.weight"), rows, C, C, lda=C, ldb=C, bias=self._p(name + ".proj_out.bias"), c_f32=out, ldc=C, resid=x)
         return out
-
 
 
 class VAEEncoder(_VAENet):
@@ -549,12 +485,11 @@ class VAEEncoder(_VAENet):
     sample) or fp32 [B, 3, H, W] in [-1, 1]."""
 
     _CONFIG_KEYS = _VAENet._CONFIG_KEYS + (("in_channels", "in_channels"),)
+    _UNTILED = " (tiled encoding is not supported)"
 
     def __init__(self, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, in_channels=3, attn_resolutions=(), device="cuda",
                  max_chunk_bytes=1 << 30, resolution=256):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.SfronError("VAEEncoder needs a GPU (no CPU fallback)")
+        super().__init__(device)
         if ch % 32:
             raise ValueError("GroupNorm(32) needs ch % 32 == 0")
         self.ch, self.ch_mult, self.z, self.in_channels = ch, tuple(ch_mult), z_channels, in_channels
@@ -580,12 +515,6 @@ class VAEEncoder(_VAENet):
                 res_h, res_w = res_h // 2, res_w // 2
         return big
 
-    def chunk_size(self, H, W):
-        ps = self.per_sample_bytes(H, W)
-        if ps >= _LIMIT:
-            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB (tiled encoding is not supported)")
-        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
-
     def _chunk(self, images, flip, lo, hi, mom_f32, mom_f16, eps, scale, lat):
         """Encoder + quant_conv (+ posterior sample) of samples [lo, hi) of the batch, results written at their batch offset."""
         L, B = _L(), hi - lo
@@ -593,14 +522,14 @@ class VAEEncoder(_VAENet):
             H, W = images.shape[1], images.shape[2]
             xr = self._buf("bf_in", B * H * W * 8, torch.bfloat16)
             src = images[lo:hi]
-            _guard(src, xr)
+            guard(src, xr)
             check(L.sfron_image_u8_to_rows_bf16(ptr(src), B, H, W, ptr(flip[lo:hi]) if flip is not None else None, 8, ptr(xr), stream_ptr()),
                   "image_u8_to_rows_bf16")
         else:
             H, W = images.shape[2], images.shape[3]
             xr = self._buf("bf_in", B * H * W * 8, torch.bfloat16)
             src = images[lo:hi]
-            _guard(src, xr)
+            guard(src, xr)
             check(L.sfron_nchw_to_rows_bf16(ptr(src), B, self.in_channels, H * W, 8, ptr(xr), stream_ptr()), "nchw_to_rows")
         cur, spare = "f_x0", "f_x1"
         x = self._conv3(xr, B, H, W, "conv_in", H, W, cur)
@@ -710,12 +639,11 @@ class VAEDecoder(_VAENet):
     (``vae.decode(z / 0.18215).sample``); ``decode_u8`` the uint8 bytes a PNG holds, per image or as the make_grid canvas."""
 
     _CONFIG_KEYS = _VAENet._CONFIG_KEYS + (("out_channels", "out_ch"),)
+    _UNTILED = " (tiled decoding is not supported)"
 
     def __init__(self, ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3, attn_resolutions=(), device="cuda",
                  max_chunk_bytes=1 << 30, resolution=256):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.SfronError("VAEDecoder needs a GPU (no CPU fallback)")
+        super().__init__(device)
         if ch % 32:
             raise ValueError("GroupNorm(32) needs ch % 32 == 0")
         if z_channels > 16:
@@ -747,12 +675,6 @@ class VAEDecoder(_VAENet):
                 big = max(big, h * w * op[2] * 4)
         return big
 
-    def chunk_size(self, H, W):
-        ps = self.per_sample_bytes(H, W)
-        if ps >= _LIMIT:
-            raise ValueError(f"one {H}x{W} image needs a {ps}-byte operand: above 2 GiB (tiled decoding is not supported)")
-        return max(1, min(self.max_chunk_bytes, _LIMIT - 1) // ps)
-
     def _chunk(self, z, lo, hi, scale):
         """post_quant_conv + Decoder of samples [lo, hi): returns the conv_out rows [B*H*W][8] fp32 (a workspace view)."""
         L, B = _L(), hi - lo
@@ -760,7 +682,7 @@ class VAEDecoder(_VAENet):
         v = self.conv3["conv_in"]
         zr = self._buf("bf_in", B * h * w * v["cip"], torch.bfloat16)
         src = z[lo:hi]
-        _guard(src, zr)
+        guard(src, zr)
         check(L.sfron_vae_latent_in(ptr(src), B, self.z, h * w, self._p("post_quant_conv.weight"), self._p("post_quant_conv.bias"),
                                     float(scale), v["cip"], ptr(zr), None, stream_ptr()), "vae_latent_in")
         cur, spare = "f_x0", "f_x1"
@@ -798,7 +720,7 @@ class VAEDecoder(_VAENet):
             hi = min(B, lo + n)
             rows = self._chunk(z, lo, hi, scale)
             dst = out[lo:hi]
-            _guard(rows, dst)
+            guard(rows, dst)
             check(_L().sfron_rows_to_nchw(ptr(rows), rows.shape[1], hi - lo, self.out_ch, H * W, ptr(dst), stream_ptr()), "rows_to_nchw")
         return out
 
@@ -823,7 +745,7 @@ class VAEDecoder(_VAENet):
         for lo in range(0, B, n):
             hi = min(B, lo + n)
             rows = self._chunk(z, lo, hi, scale)
-            _guard(rows, out)
+            guard(rows, out)
             check(_L().sfron_rows_to_image_u8(ptr(rows), rows.shape[1], hi - lo, H, W, m, lo_v, hi_v, int(nrow), int(padding), lo, B,
                                                ptr(out), stream_ptr()), "rows_to_image_u8")
         return out
