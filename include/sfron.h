@@ -969,6 +969,42 @@ int sfron_layernorm_fwd_f32(const float* x, const float* gamma, const float* bet
  * table that slipped past gives wrong pixels, never an access outside src, tmp or dst. */
 int sfron_image_resample_u8(const uint8_t* src, int Hs, int Ws, const int32_t* kx, const int32_t* bx, int ksx, const int32_t* ky,
                             const int32_t* by, int ksy, int Wo, int Ho, uint8_t* tmp, int64_t tmp_bytes, uint8_t* dst, void* stream);
+/* The batched form (csrc/resample.hip): chains of such resizes -- ADM's center_crop_arr is BOX halvings, then BICUBIC, then the crop,
+ * sfron.resample.center_crop_plan -- for a whole batch of images of different sizes, in a number of launches that does not depend on the
+ * batch.  The arithmetic per pass is exactly that of sfron_image_resample_u8, and the device code is shared with it.
+ *   pool .... device bytes holding the sources, each uint8 [h][w][3] at its own byte offset (any alignment)
+ *   tables .. device int32 blob of n_tables words holding every coefficient table [n][ksize] and bounds table [n][2] the passes use
+ *   passes .. device array of n_passes records, one per image, stage and axis, grouped by level
+ *   work .... device bytes for everything between a source and a result; out: device bytes the last vertical pass of each image writes
+ * A stage is a horizontal pass (level 2s) and a vertical pass over its result (level 2s + 1); an image counts its stages from its own
+ * first one, so an image with fewer stages finishes in an earlier level.  One launch per level: n_levels = 2 * (most stages of an image).
+ * level_first / level_rows / level_cols are HOST arrays, read during the call: level l holds passes level_first[l] ..
+ * level_first[l + 1] - 1 (level_first has n_levels + 1 entries, from 0 to n_passes, strictly ascending); level_rows[l] is the largest
+ * row count of its passes (horizontal: nrows; vertical: n_out) and level_cols[l] the largest extent along a row (horizontal: n_out
+ * pixels; vertical: 3 * in_w bytes).  The grid of a level spans them and a workgroup beyond its own pass's extents exits.
+ * No allocation, no synchronisation (graph-capturable), 64-bit offsets, plain vector stores.
+ * Who checks what, as for sfron_image_resample_u8.  SFRON_ERR_ARG before any launch, with work / out untouched: a null pointer, a
+ * non-positive count or size, an odd n_levels, a level list that does not ascend from 0 to n_passes, a level of more than 65535 passes
+ * or 65535 * 256 columns, or a pool / work / out below what the largest extents imply (pool: 3 * level_rows[0]; work: 3 * the larger
+ * extent of every horizontal level; out: 3 * level_rows and level_cols of the last level).  The records are device data: the wrapper
+ * (sfron.resample.image_resample_batch_u8, same status, before the upload) checks bounds inside their input, ascending row bounds,
+ * offsets and extents inside pool / work / out / tables, and that no pass reads or writes what another pass of its level writes.
+ * Behind that the kernels clamp every offset, extent and bound they read from a record or a table into the buffer it addresses. */
+enum { SFRON_RESAMPLE_POOL = 0, SFRON_RESAMPLE_WORK = 1, SFRON_RESAMPLE_OUT = 2 };
+typedef struct sfron_resample_pass {     /* 16 x int64 */
+  int64_t in_buf, in_off;                /* input: SFRON_RESAMPLE_POOL (horizontal passes only) or _WORK, and its byte offset there */
+  int64_t in_w, in_h;                    /* pixels per row and rows of the input held at in_off (a window of the previous stage, or a source) */
+  int64_t out_buf, out_off;              /* output: _WORK, or _OUT (vertical passes only), and its byte offset; rows are packed */
+  int64_t n_out;                         /* outputs along the axis: columns of a horizontal pass, rows of a vertical one */
+  int64_t org;                           /* the index the bounds count from: the first column (horizontal) / row (vertical) held at in_off */
+  int64_t row0, nrows;                   /* horizontal: the input rows it resamples, [row0, row0 + nrows) of in_h, written as rows 0 .. nrows - 1 */
+  int64_t k_off, b_off, ksize;           /* word offsets of coefficients [n_out][ksize] and bounds [n_out][2] in tables */
+  int64_t reserved[3];
+} sfron_resample_pass;
+int sfron_image_resample_batch_u8(const uint8_t* pool, int64_t pool_bytes, const int32_t* tables, int64_t n_tables,
+                                  const sfron_resample_pass* passes, int n_passes, const int32_t* level_first, const int32_t* level_rows,
+                                  const int32_t* level_cols, int n_levels, uint8_t* work, int64_t work_bytes, uint8_t* out, int64_t out_bytes,
+                                  void* stream);
 
 /* ------------------------------------------------------------------ DDPM guided sampling (ddpm_sample.hip)
  * Classifier-free guidance + one generalized step of DDPM/functions/denoising.py:72-95 in one pass:

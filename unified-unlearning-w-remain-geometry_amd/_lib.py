@@ -312,6 +312,10 @@ _PROTOS.update({
                                 c_int, c_float, _P, c_int64, _S]),
 })
 _PROTOS["sfron_image_resample_u8"] = (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, _S])
+# (pool, pool_bytes, tables, n_tables, passes, n_passes, level_first / level_rows / level_cols: host int32 arrays, n_levels, work, work_bytes,
+#  out, out_bytes, stream)
+_PROTOS["sfron_image_resample_batch_u8"] = (c_int, [_P, c_int64, _P, c_int64, _P, c_int, _P, _P, _P, c_int, _P, c_int64, _P, c_int64, _S])
+RESAMPLE_POOL, RESAMPLE_WORK, RESAMPLE_OUT = range(3)        # include/sfron.h SFRON_RESAMPLE_*
 _PROTOS.update({
     "sfron_ddpm_guided_step": (c_int, [_P, _P, _P, _P, c_double, _P, c_int, _P, c_int64, _P, _P, _S]),
     "sfron_ddpm_sampler_advance": (c_int, [_P, c_int, _P, _P, c_int, _S]),

@@ -196,14 +196,28 @@ def load_image(path, image_size):
     return np.asarray(center_crop_arr(img, image_size), dtype=np.uint8)
 
 
+def decode_image(path):
+    """pil_loader alone: the decoded RGB pixels, uint8 [H, W, 3] (every mode arrives as RGB), for the device crop (resample.center_crop_gpu)."""
+    with open(path, "rb") as fh:
+        return np.asarray(Image.open(fh).convert("RGB"), dtype=np.uint8)
+
+
 def _pool(workers):
     return ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_HOST_THREADS)))
 
 
-def encode_image_folder(data_path, encoder, cache_dir, image_size=256, batch=32, dtype=np.float32, workers=8):
+def encode_image_folder(data_path, encoder, cache_dir, image_size=256, batch=32, dtype=np.float32, workers=8, gpu_resize=False):
     """``data_path/train/<class>/*`` -> one write_shard per class of the encoder's posterior moments (what LatentCache and
     UnlearnLatentLoader read), files in ImageFolder order.  Images are decoded and cropped on a host thread pool while the
-    previous batch encodes on the device.  Returns {class name: image count}."""
+    previous batch encodes on the device; with ``gpu_resize`` the pool only decodes and the centre crop runs on the device
+    (resample.center_crop_gpu: the same bytes, so the same shards).  Returns {class name: image count}."""
+    if gpu_resize:
+        from . import resample
+        load = decode_image
+        crop = lambda imgs: resample.center_crop_gpu(imgs, image_size, device=encoder.dev)
+    else:
+        load = lambda f: load_image(f, image_size)
+        crop = lambda imgs: torch.from_numpy(np.stack(imgs))
     classes, class_to_idx = find_classes(os.path.join(data_path, "train"))
     mdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[np.dtype(dtype)]
     counts = {}
@@ -211,11 +225,11 @@ def encode_image_folder(data_path, encoder, cache_dir, image_size=256, batch=32,
         for c in classes:
             files = class_files(os.path.join(data_path, "train", c))
             parts = []
-            nxt = pool.map(lambda f: load_image(f, image_size), files[:batch]) if files else None
+            nxt = pool.map(load, files[:batch]) if files else None
             for lo in range(0, len(files), batch):
-                imgs = np.stack(list(nxt))
-                nxt = pool.map(lambda f: load_image(f, image_size), files[lo + batch:lo + 2 * batch]) if lo + batch < len(files) else None
-                parts.append(encoder.moments(torch.from_numpy(imgs), dtype=mdt).cpu().numpy())
+                imgs = list(nxt)
+                nxt = pool.map(load, files[lo + batch:lo + 2 * batch]) if lo + batch < len(files) else None
+                parts.append(encoder.moments(crop(imgs), dtype=mdt).cpu().numpy())
             if not parts:
                 raise FileNotFoundError(f"class {c!r} has no image files")
             write_shard(cache_dir, c, class_to_idx[c], np.concatenate(parts))
@@ -229,10 +243,15 @@ class UnlearnImageLoader:
     265-267,305-307: centre crop, RandomHorizontalFlip, ToTensor + Normalize, vae.encode(x).latent_dist.sample().mul_(0.18215)).
     Sample ids, shuffling and the t / noise / eps / drop draws equal the cache route's; the flips are drawn after them, so with
     ``flip_prob=0`` every field but x0 equals UnlearnLatentLoader's bit for bit.  The next batch is decoded on host threads and copied
-    on a side stream while the current one is consumed."""
+    on a side stream while the current one is consumed.
+
+    ``gpu_resize=True`` moves the centre crop to the device, with the same bytes (resample.center_crop_gpu's parts): the pool threads
+    only decode, the batch-ahead thread plans the batch and gathers its pixels, tables and pass records into a pinned buffer
+    (resample.CropStaging: a batch being assembled never waits for the one being consumed), ``next`` uploads it on the copy stream and
+    runs the level launches, then the encoder, on the caller's stream."""
 
     def __init__(self, data_path, forget_class, encoder, global_batch, rank=0, world=1, seed=0, image_size=256, flip_prob=0.5,
-                 num_timesteps=1000, drop_prob=0.1, scale=0.18215, device="cuda", workers=8):
+                 num_timesteps=1000, drop_prob=0.1, scale=0.18215, device="cuda", workers=8, gpu_resize=False):
         assert global_batch % world == 0
         self.enc, self.gb, self.rank, self.world, self.seed = encoder, global_batch, rank, world, seed
         self.size, self.flip_prob, self.T, self.p, self.scale = image_size, float(flip_prob), num_timesteps, drop_prob, scale
@@ -250,40 +269,56 @@ class UnlearnImageLoader:
         self._pool = _pool(workers)                # decodes the images of a batch
         self._bg = ThreadPoolExecutor(max_workers=1)   # assembles the next batch (its own thread: it waits on _pool's tasks)
         self._ahead, self._pinned = {}, None
+        self.gpu_resize = bool(gpu_resize)
+        if self.gpu_resize:
+            from . import resample
+            self._crop = resample.crop_staging(self.dev)
 
-    def _host_batch(self, stream, step):
+    def _host_batch(self, stream, step, gather=False):
         s = self.sets[stream]
         C, h, w = self.lat_shape
         ids, t, noise, eps, drop, g2 = _batch_draws(self.seed, stream, step, len(s), self.gb, self.T, self.p, C, h, w)
         flip = (torch.rand(self.gb, generator=g2) < self.flip_prob).to(torch.uint8)
         mine = list(range(self.rank, self.gb, self.world))
-        imgs = np.stack(list(self._pool.map(lambda j: load_image(s[int(ids[j])][0], self.size), mine)))
         y = torch.tensor([s[int(ids[j])][1] for j in mine], dtype=torch.int64)
-        return dict(images=torch.from_numpy(imgs), flip=flip[mine].contiguous(), eps=eps[mine].contiguous(), y=y, t=t[mine].contiguous(),
-                    noise=noise[mine].contiguous(), drop=drop[mine].contiguous())
+        hb = dict(flip=flip[mine].contiguous(), eps=eps[mine].contiguous(), y=y, t=t[mine].contiguous(), noise=noise[mine].contiguous(),
+                  drop=drop[mine].contiguous())
+        if self.gpu_resize:
+            hb["sources"] = list(self._pool.map(lambda j: decode_image(s[int(ids[j])][0]), mine))
+            if gather:                              # (the batch-ahead thread: plan and fill the pinned buffer)
+                hb["gathered"] = self._crop.gather(hb.pop("sources"), self.size)
+        else:
+            imgs = np.stack(list(self._pool.map(lambda j: load_image(s[int(ids[j])][0], self.size), mine)))
+            hb = dict(images=torch.from_numpy(imgs), **hb)
+        return hb
 
     def _stage(self, hb):
+        gathered = hb.pop("gathered", None)
         pinned = {k: v.pin_memory() for k, v in hb.items()}
         with torch.cuda.stream(self._copy):
             dv = {k: v.to(self.dev, non_blocking=True) for k, v in pinned.items()}
+            if gathered is not None:
+                dv["crop_bytes"] = gathered.upload()
             ev = torch.cuda.Event()
             ev.record(self._copy)
-        return dv, (ev, pinned)
+        return dv, (ev, pinned), gathered
 
     def host_batch(self, stream, step):
-        """The host side of batch `step` of `stream` (uint8 images [n, S, S, 3], flips and the draws), for tests and tools."""
+        """The host side of batch `step` of `stream` (uint8 images [n, S, S, 3], flips and the draws), for tests and tools; with
+        ``gpu_resize`` the decoded sources (a list of uint8 [H, W, 3]) stand in place of ``images``."""
         return self._host_batch(stream, step)
 
     def next(self, stream):
         step = self.step[stream]
         fut = self._ahead.pop((stream, step), None)
-        hb = fut.result() if fut is not None else self._host_batch(stream, step)
-        self._ahead[(stream, step + 1)] = self._bg.submit(self._host_batch, stream, step + 1)     # decode one batch ahead
+        hb = fut.result() if fut is not None else self._host_batch(stream, step, True)
+        self._ahead[(stream, step + 1)] = self._bg.submit(self._host_batch, stream, step + 1, True)     # decode one batch ahead
         self.step[stream] = step + 1
-        dv, (ev, self._pinned) = self._stage(hb)     # (the pinned batch lives until the next call)
+        dv, (ev, self._pinned), gathered = self._stage(hb)     # (the pinned batch lives until the next call)
         cur = torch.cuda.current_stream()
         cur.wait_event(ev)
         for v in dv.values():
             v.record_stream(cur)
-        x0 = self.enc.encode(dv["images"], eps=dv["eps"], flip=dv["flip"], scale=self.scale)
+        images = dv["images"] if gathered is None else gathered.run(dv["crop_bytes"])      # (the level launches, on the caller's stream)
+        x0 = self.enc.encode(images, eps=dv["eps"], flip=dv["flip"], scale=self.scale)
         return dict(x0=x0, y=dv["y"], t=dv["t"], noise=dv["noise"], drop=dv["drop"])
