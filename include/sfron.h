@@ -562,7 +562,9 @@ int64_t sfron_groupnorm_scratch_bytes(int B, int HW, int C, int groups);
 int sfron_softmax_fwd(const float* s, int64_t rows, int n, int n_valid /* keys; columns beyond get probability 0 */, float scale, uint16_t* p,
                       void* stream);
 /* y = bf16(LayerNorm(x; eps) * gamma + beta) on fp32 rows [rows][D]; backward: dx (+)=, per-block partial sums of d gamma / d beta
- * [ceil(rows / sfron_layernorm_rows_per_block(rows))][D] (BasicTransformerBlock.norm1..3, SD/ldm/modules/attention.py:223-225) */
+ * [ceil(rows / sfron_layernorm_rows_per_block(rows))][D] (BasicTransformerBlock.norm1..3, SD/ldm/modules/attention.py:223-225).
+ * The backward entries take D <= 2048 (their per-wave column accumulators fill the 64 KiB of dynamic LDS a launch gets by default
+ * there) and return SFRON_ERR_ARG above it, as they do for extra == dx, with nothing written. */
 int sfron_layernorm_fwd(const float* x, const float* gamma, const float* beta, int64_t rows, int D, float eps, uint16_t* y, float* mean,
                         float* rstd, void* stream);
 int sfron_layernorm_rows_per_block(int64_t rows);

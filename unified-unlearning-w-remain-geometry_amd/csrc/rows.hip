@@ -645,7 +645,9 @@ int sfron_layernorm_bwd(const float* dy, const float* x, const float* gamma, con
 }
 int sfron_layernorm_bwd_res(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, int64_t rows, int D, float* dx,
                             int accumulate, const float* extra, float* part_gamma, float* part_beta, void* stream) {
-  SFRON_CHECK_ARG(dy && x && gamma && mean && rstd && dx && part_gamma && part_beta && rows > 0 && D > 0 && D <= 4096);
+  // D <= 2048: the [4 waves][2][D] fp32 accumulators are dynamic LDS, 64 KiB at D = 2048 -- the most a launch gets without raising
+  // MaxDynamicSharedMemorySize, which this launcher does not do (no model here has a wider LayerNorm)
+  SFRON_CHECK_ARG(dy && x && gamma && mean && rstd && dx && part_gamma && part_beta && rows > 0 && D > 0 && D <= 2048);
   SFRON_CHECK_ARG(extra != dx);
   const int rpb = sfron_layernorm_rows_per_block(rows);
   const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
