@@ -1074,6 +1074,45 @@ int sfron_dit_sample_step(const float* x, const float* model_out, const int64_t*
 int sfron_dit_sampler_advance(const int64_t* order, const int64_t* timestep_map, int steps, int map_len, int32_t* step, int64_t* t_idx, int n,
                               int64_t* t_model, int rows, void* stream);
 
+/* ------------------------------------------------------------------ DiT likelihood evaluation (dit_bpd.hip)
+ * One term of calc_bpd_loop (DiT/diffusion/gaussian_diffusion.py:805-858) for the LEARNED_RANGE / EPSILON model, forward only: nothing is
+ * frozen, no gradient is written.  fp32 in the reference's operation order, 64-bit element offsets, one workgroup per sample, one launch.
+ *   x0        [n][C][hw]
+ *   x_t       [n][C][hw] or NULL: NULL recomputes x_t = sqrt_ac * x0 + sqrt_1m_ac * noise in registers, the expression (and, the library
+ *             being built with -ffp-contract=off, the bits) of sfron_q_sample
+ *   noise     [n][C][hw] this step's noise; may be NULL when x_t is given (then mse must be NULL).  One of x_t / noise is required.
+ *   model_out [n][2C][hw]: channels 0..C-1 epsilon, C..2C-1 the variance interpolation v
+ *   t         DEVICE int64 [n]: PER-ROW indices into tab
+ *   tab       DEVICE float [T][8]: sfron_dit_loss_fwd_bwd's table
+ *   vb, xstart_mse, mse   row-major [n][ld] matrices (xstart_mse and mse may be NULL); sample i's terms go to element [i][k], k = *step
+ *             when step (DEVICE int32, the counter sfron_dit_sampler_advance keeps) is given, else col.  In calc_bpd_loop ld = T and
+ *             column 0 is t = T - 1, as the reference stacks them.
+ *     vb          mean_flat(normal_kl(true posterior, model)) / ln 2, or for a row with t == 0 the discretized decoder NLL (:699-712,
+ *                 diffusion_utils.py:62-88: the 1e-12 clamp and the +-0.999 edges); pred_xstart = sqrt_recip_ac * x_t - sqrt_recipm1_ac *
+ *                 eps_hat is clamped to [-1, 1] before the model mean when clip_denoised != 0, as p_mean_variance does
+ *     xstart_mse  mean_flat((pred_xstart - x0)^2)
+ *     mse         mean_flat((eps - noise)^2), eps = (sqrt_recip_ac * x_t - pred_xstart) / sqrt_recipm1_ac: _predict_eps_from_xstart of
+ *                 the (possibly clamped) pred_xstart, NOT the raw model output
+ *     The per-sample sums are accumulated and reduced in fp64 in a fixed order (no atomics): the same inputs give the same bits.
+ *   pred_xstart   [n][C][hw] or NULL
+ *   next_xt   [n][C][hw] or NULL.  Given (with next_noise [n][C][hw], order DEVICE int64 [steps], step, steps <= ld): when k + 1 < steps
+ *             the launch also writes next_xt = sqrt_ac[i] * x0 + sqrt_1m_ac[i] * next_noise, i = order[k + 1] -- sfron_q_sample's bits, the
+ *             model input of the next step, so x0 is read once per step; at the last step (k + 1 == steps) nothing is written.
+ * t, *step and order live on the device, so the host cannot refuse their values: a row whose t is outside [0, T) reads no table row and
+ * gets NaN terms (its pred_xstart is unspecified), a counter outside [0, ld) writes no term, an order entry outside [0, T) no next_xt.
+ * SFRON_ERR_ARG before any launch, outputs untouched, for: a null required pointer (x0, model_out, t, tab, vb; both of x_t and noise; mse
+ * without noise; next_xt without next_noise / order / step), a non-positive extent or T, ld <= 0, without step a col outside [0, ld), with
+ * next_xt a steps outside [1, ld], n * C * hw >= 2^31 or n * ld >= 2^31, a next_xt that aliases an input or pred_xstart, a pred_xstart
+ * that aliases x0, x_t or noise. */
+int sfron_dit_bpd_step(const float* x0, const float* x_t, const float* noise, const float* model_out, const int64_t* t, const float* tab,
+                       int T, int n, int c, int hw, int clip_denoised, float* vb, float* xstart_mse, float* mse, int ld, const int32_t* step,
+                       int col, float* pred_xstart, const float* next_noise, const int64_t* order, int steps, float* next_xt, void* stream);
+/* _prior_bpd (:789-803): prior_bpd[i] = mean_flat(normal_kl(sqrt_ac_last * x0, log_one_minus_ac_last, 0, 0)) / ln 2 -- the two scalars are
+ * sqrt_alphas_cumprod[T - 1] and log(1 - alphas_cumprod[T - 1]), the fp64 table values rounded once to fp32, passed by value.
+ * SFRON_ERR_ARG before any launch for a null pointer, a non-positive extent, n * C * hw >= 2^31 or a scalar that is not finite. */
+int sfron_dit_prior_bpd(const float* x0, int n, int c, int hw, float sqrt_ac_last, float log_one_minus_ac_last, float* prior_bpd,
+                        void* stream);
+
 /* ------------------------------------------------------------------ classifier evaluation (classify.hip)
  * What the ResNet-34 / ResNet-50 forward passes of DDPM/classifier_evaluation.py and SD/eval-scripts/imageclassify.py need beside
  * sfron_conv_fwd and the GEMM.  Every entry point: SFRON_ERR_ARG before any launch for a null pointer, a non-positive extent or an

@@ -326,6 +326,11 @@ _PROTOS.update({           # csrc/dit_sample.hip: the DiT sampler
     "sfron_dit_sampler_advance": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, c_int, _S]),
 })
 DIT_SAMPLE_DDPM, DIT_SAMPLE_DDIM, DIT_SAMPLE_DDIM_REVERSE = range(3)       # include/sfron.h SFRON_DIT_SAMPLE_*
+_PROTOS.update({           # csrc/dit_bpd.hip: the DiT likelihood evaluation
+    "sfron_dit_bpd_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, _P, _P, _P, c_int,
+                                   _P, _S]),
+    "sfron_dit_prior_bpd": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, _P, _S]),
+})
 _PROTOS.update({           # csrc/classify.hip: the ResNet evaluators
     "sfron_image_u8_patches7": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_int, _P, _S]),
     "sfron_nchw_patches7": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _S]),

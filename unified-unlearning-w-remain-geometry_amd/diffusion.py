@@ -264,6 +264,81 @@ class GaussianDiffusion:
         return final["sample"]
 
 
+    # ------------------------------------------------------------------ likelihood evaluation (gaussian_diffusion.py:682-713,789-858)
+    def bpd_step(self, x_start, model_output, t, clip_denoised=True, x_t=None, noise=None, vb=None, xstart_mse=None, mse=None, col=0,
+                 step=None, pred_xstart=None, next_noise=None, order=None, next_xt=None):
+        """One sfron_dit_bpd_step launch.  x_start [n, C, ...], model_output [n, 2C, ...], t int64 [n] (table indices, per row); x_t given,
+        or recomputed from ``noise`` (sfron_q_sample's bits).  vb / xstart_mse / mse: [n, ld] fp32 matrices whose column ``col`` (or the
+        device counter ``step``) receives the terms; vb is allocated as [n, 1] when None.  next_xt (with next_noise, order, step): the
+        launch also writes q_sample of step order[step + 1] there.  Returns vb."""
+        n, c = x_start.shape[0], x_start.shape[1]
+        assert model_output.shape[0] == n and model_output.shape[1] == 2 * c and model_output.is_contiguous() and x_start.is_contiguous()
+        if vb is None:
+            vb = torch.empty(n, 1, dtype=torch.float32, device=x_start.device)
+        ld = vb.shape[1]
+        assert all(m is None or (m.shape == vb.shape and m.is_contiguous()) for m in (vb, xstart_mse, mse))
+        check(_lib.lib().sfron_dit_bpd_step(ptr(x_start), ptr(x_t), ptr(noise), ptr(model_output), ptr(t), ptr(self.tab), self.num_timesteps,
+                                            n, c, x_start[0, 0].numel(), int(bool(clip_denoised)), ptr(vb), ptr(xstart_mse), ptr(mse), ld,
+                                            ptr(step), int(col), ptr(pred_xstart), ptr(next_noise), ptr(order),
+                                            0 if order is None else order.numel(), ptr(next_xt), stream_ptr()), "dit_bpd_step")
+        return vb
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """Reference signature (gaussian_diffusion.py:682): {"output": [N] bits per dimension (the KL term, or the decoder NLL where
+        t == 0), "pred_xstart"}.  ``t`` is per row; the model sees the original timesteps of a respaced process."""
+        x_start, x_t = x_start.contiguous().float(), x_t.contiguous().float()
+        t = t.contiguous()
+        model_output = self._wrap_model(model)(x_t, t, **(model_kwargs or {}))
+        if isinstance(model_output, tuple):
+            model_output = model_output[0]
+        n, c = x_t.shape[0], x_t.shape[1]
+        assert t.shape == (n,) and model_output.shape == (n, 2 * c, *x_t.shape[2:])
+        mo = model_output.contiguous().float()                              # named: temporaries must outlive the launch
+        pred = torch.empty_like(x_t)
+        vb = self.bpd_step(x_start, mo, t, clip_denoised, x_t=x_t, pred_xstart=pred)
+        return {"output": vb.view(n), "pred_xstart": pred}
+
+    def _prior_bpd(self, x_start):
+        """Reference signature (gaussian_diffusion.py:789): the prior KL term in bits per dimension, [N]."""
+        x_start = x_start.contiguous().float()
+        n = x_start.shape[0]
+        ac = self.tables["alphas_cumprod"][-1]
+        out = torch.empty(n, dtype=torch.float32, device=x_start.device)
+        check(_lib.lib().sfron_dit_prior_bpd(ptr(x_start), n, x_start.shape[1], x_start[0, 0].numel(), float(np.float32(np.sqrt(ac))),
+                                             float(np.float32(np.log(1.0 - ac))), ptr(out), stream_ptr()), "dit_prior_bpd")
+        return out
+
+    def _bpd_result(self, x_start, vb, xstart_mse, mse):
+        prior_bpd = self._prior_bpd(x_start)
+        return {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    @torch.no_grad()
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, generator=None, step_noise=None):
+        """Reference signature (gaussian_diffusion.py:805) for any callable model: total_bpd [N], prior_bpd [N], vb / xstart_mse / mse
+        [N, T] with column 0 the term of t = T - 1.  Step k's noise is ``step_noise[k]`` if given, else drawn from ``generator`` (None:
+        ``randn_like(x_start)``, as the reference draws).  One sfron_q_sample, one model call and one sfron_dit_bpd_step per step."""
+        x_start = x_start.contiguous().float()
+        n, T, dev = x_start.shape[0], self.num_timesteps, x_start.device
+        vb, xstart_mse, mse = (torch.empty(n, T, dtype=torch.float32, device=dev) for _ in range(3))
+        wrapped = self._wrap_model(model)
+        for k, i in enumerate(list(range(T))[::-1]):
+            t = torch.tensor([i] * n, device=dev)
+            if step_noise is not None:
+                noise = step_noise[k].to(dev, torch.float32).contiguous()
+            elif generator is not None:
+                noise = torch.randn(x_start.shape, generator=generator, device=generator.device).to(dev)
+            else:
+                noise = torch.randn_like(x_start)
+            x_t = self.q_sample(x_start, t, noise)
+            model_output = wrapped(x_t, t, **(model_kwargs or {}))
+            if isinstance(model_output, tuple):
+                model_output = model_output[0]
+            assert model_output.shape == (n, 2 * x_start.shape[1], *x_start.shape[2:])
+            mo = model_output.contiguous().float()
+            self.bpd_step(x_start, mo, t, clip_denoised, noise=noise, vb=vb, xstart_mse=xstart_mse, mse=mse, col=k)
+        return self._bpd_result(x_start, vb, xstart_mse, mse)
+
+
 class _DitLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model_output, diff, x_start, t, noise):

@@ -23,7 +23,42 @@ from .diffusion import create_diffusion
 DEFAULT_CLASS_LABELS = (207, 360, 387, 974, 88, 979, 417, 279)       # DiT/sample.py:47
 
 
-class DiTSampler:
+class _OwnEngine:
+    """A forward-only engine of the holder's own over the arenas of ``self.model``'s engine: what DiTSampler and
+    dit_bpd.DiTBpdEvaluator run the model on."""
+    _eng = _eng_key = None
+
+    def _engine(self, rows):
+        """The holder's own engine at batch ``rows`` over the arenas of the model's CURRENT engine (rebuilt when the batch size, the
+        arenas or the armed fp8 state changed since the last call)."""
+        from .engine import DitEngine
+        eng = self.model.engine
+        key = (rows, eng.params.data_ptr(), eng.grads.data_ptr(), id(eng.fp8), eng.fp8_wgrad is not None)
+        if self._eng is None or self._eng_key != key:
+            self.close()
+            samp = DitEngine(rows, share=eng, grads=eng.grads, **eng._ctor)       # forward only: the gradient arena is never written
+            try:
+                samp._share_fp8(eng)
+            except Exception:
+                samp.close()
+                raise
+            self._eng, self._eng_key = samp, key
+        return self._eng
+
+    def close(self):
+        """Release the holder's engine (idempotent)."""
+        if self._eng is not None:
+            self._eng.close()
+        self._eng = self._eng_key = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown
+            pass
+
+
+class DiTSampler(_OwnEngine):
     """Guided sampling of a ``dit.DiT`` at batch 2n (row i conditional, row i + n the null label), or unguided at batch n for
     ``cfg_scale <= 1.0`` (the choice of sample_ddp.py:114-122: ``model.forward`` instead of ``forward_with_cfg``).
 
@@ -50,36 +85,6 @@ class DiTSampler:
         self.cfg_scale, self.n_guided, self.mode, self.eta = float(cfg_scale), int(n_guided), mode, float(eta)
         self.clip_denoised = bool(clip_denoised)
         self.guided = self.cfg_scale > 1.0
-        self._eng = self._eng_key = None
-
-    def _engine(self, rows):
-        """The sampler's own engine at batch ``rows`` over the arenas of the model's CURRENT engine (rebuilt when the batch size, the
-        arenas or the armed fp8 state changed since the last call)."""
-        from .engine import DitEngine
-        eng = self.model.engine
-        key = (rows, eng.params.data_ptr(), eng.grads.data_ptr(), id(eng.fp8), eng.fp8_wgrad is not None)
-        if self._eng is None or self._eng_key != key:
-            self.close()
-            samp = DitEngine(rows, share=eng, grads=eng.grads, **eng._ctor)       # forward only: the gradient arena is never written
-            try:
-                samp._share_fp8(eng)
-            except Exception:
-                samp.close()
-                raise
-            self._eng, self._eng_key = samp, key
-        return self._eng
-
-    def close(self):
-        """Release the sampler's engine (idempotent)."""
-        if self._eng is not None:
-            self._eng.close()
-        self._eng = self._eng_key = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:          # interpreter shutdown
-            pass
 
     def needs_noise(self):
         return self.mode == "ddpm" or self.eta != 0.0
