@@ -232,13 +232,13 @@ def check_e4m3(got_bytes, ref64, ref32, scale, name=None, margin=MARGIN):
 # ------------------------------------------------------------------------------------------------ guarded device buffers
 GUARD_BYTES = 4096
 _SENT = {torch.float32: (torch.int32, 0x7FC00A5A), torch.bfloat16: (torch.int16, 0x7FC5),
-         torch.uint8: (torch.uint8, 0xA5), torch.int32: (torch.int32, 0x25A5A5A5)}
+         torch.uint8: (torch.uint8, 0xA5), torch.int32: (torch.int32, 0x25A5A5A5), torch.int64: (torch.int64, 0x25A5A5A5A5A5A5A5)}
 
 
 def guarded(shape, dtype, ld=None, device="cuda:0"):
     """-> (view, check).  `view` has `shape`, rows `ld` elements apart (default: dense), starts 16-byte aligned and lies inside one
     allocation whose every other element -- the gaps between rows and GUARD_BYTES before and after -- holds a sentinel (NaN for fp32, a
-    NaN bit pattern for bf16, 0xA5 bytes); the view itself starts out as sentinels too.  check(what) asserts that every sentinel outside
+    NaN bit pattern for bf16, 0xA5 bytes, 0x25A5.. words for int32 / int64); the view itself starts out as sentinels too.  check(what) asserts that every sentinel outside
     the view is unchanged.  check.full / check.inside give the whole allocation's bits and the view's place in it."""
     shape = tuple(shape)
     width = shape[-1]
