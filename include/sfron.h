@@ -1143,6 +1143,31 @@ int sfron_pool_fc(const float* x, int ld, int B, int HW, int C, const float* w, 
 int sfron_classify_metrics(const float* logits, int ld, int B, int n_cls, int target, int topk, float* probs, float* entropy, float* p_target,
                            int32_t* argmax, float* topk_p, int32_t* topk_i, void* stream);
 
+/* ------------------------------------------------------------------ DDPM training batches from a resident dataset (ddpm_data.hip)
+ * One launch makes the inputs of a DDPMSFRon stage from a uint8 dataset that lives on the device: what DataLoader's collate, the
+ * upload, ToTensor, RandomHorizontalFlip, data_transform (DDPM/dataset/__init__.py:241-255) and the antithetic timestep draw
+ * (DDPM/runners/diffusion.py) do per batch on the host.
+ *   images ... uint8 [N][C][H][W];  labels int64 [N]
+ *   idx ...... DEVICE int64 [B]: image b of the batch is images[idx[b]]
+ *   flip ..... DEVICE uint8 [B] or NULL: non-zero mirrors image b left to right (x0[.., w] = image[.., W - 1 - w])
+ *   u, n ..... fp32 [B][C][H][W], the torch.rand_like / torch.randn_like draws; read only when uniform_deq / gaussian_deq != 0
+ *   mode ..... SFRON_DDPM_DATA_PLAIN, _RESCALED (2 X - 1) or _LOGIT (logit_transform, lam = 1e-6)
+ *   image_mean fp32 [C][H][W] or NULL (subtracted last)
+ *   t_half ... DEVICE int64 [B / 2 + 1] with t int64 [B], or both NULL: t = cat(t_half, T - t_half - 1)[:B]
+ *   x0 fp32 [B][C][H][W], c int64 [B] = labels[idx[b]]
+ * Arithmetic: fp32, one IEEE operation per torch op in the reference's order and no contraction: X = byte / 255 (a correctly rounded
+ * division), X / 256 * 255 + u / 256, X + n * 0.01f, 2 X - 1 or lam + (1 - 2 lam) X followed by log(X) - log1p(-X), X - mean.  Every form
+ * but _LOGIT gives the bits of the torch expression; _LOGIT differs from it by the error of the device's logf / log1pf.
+ * idx is device data and cannot be refused: an idx[b] outside [0, N) reads nothing, its x0 row becomes NaN and c[b] = -1.
+ * When W % 4 == 0 and images / u / n / image_mean / x0 are 4 / 16-byte aligned a lane moves four pixels (one dword in, 16 bytes out);
+ * any other width or alignment takes a one-pixel path with the same bits.  64-bit offsets.
+ * SFRON_ERR_ARG before any launch, outputs untouched: a null required pointer (images, labels, idx, x0, c; u or n where its flag is
+ * set; one of t_half / t without the other), a non-positive N, C, H, W or B, B * C * H * W >= 2^31, T <= 0, an unknown mode. */
+enum { SFRON_DDPM_DATA_PLAIN = 0, SFRON_DDPM_DATA_RESCALED = 1, SFRON_DDPM_DATA_LOGIT = 2 };
+int sfron_ddpm_batch_u8(const uint8_t* images, const int64_t* labels, int64_t N, int C, int H, int W, const int64_t* idx,
+                        const uint8_t* flip, int B, int uniform_deq, const float* u, int gaussian_deq, const float* n, int mode,
+                        const float* image_mean, const int64_t* t_half, int T, float* x0, int64_t* c, int64_t* t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -339,6 +339,11 @@ _PROTOS.update({           # csrc/classify.hip: the ResNet evaluators
     "sfron_pool_fc": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _S]),
     "sfron_classify_metrics": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _S]),
 })
+DDPM_DATA_PLAIN, DDPM_DATA_RESCALED, DDPM_DATA_LOGIT = range(3)            # include/sfron.h SFRON_DDPM_DATA_*
+_PROTOS.update({           # csrc/ddpm_data.hip: DDPM training batches from a resident dataset
+    "sfron_ddpm_batch_u8": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P,
+                                    _P, _S]),
+})
 _PROTOS.update({           # csrc/plms.hip: the ldm PLMS sampler
     "sfron_plms_cfg_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _S]),
     "sfron_inpaint_blend": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, c_float, c_float, _P, _S]),

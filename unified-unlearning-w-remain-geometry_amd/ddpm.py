@@ -497,6 +497,23 @@ class DDPMSFRon:
         self._weights_updated()
         return {"forget_loss": ori_forget, "remain_loss": ori_remain, "alpha": alpha}
 
+    def _train_pass(self, **batch):
+        loss = self._loss(batch, "simple")
+        self._backward(loss)
+        return loss.detach()
+
+    def train_step(self, batch):
+        """One iteration of ``train`` / ``retrain`` (DDPM/runners/diffusion.py:121-157, :202-237): the plain loss on one batch, clip, Adam,
+        EMA update -- the remain stage of ``step`` without remain_alpha, in the same one-launch sweep.  The mask plays no part."""
+        self.model.train()
+        keys = ("x0", "c", "t", "e", "keep_mask")
+        loss = self._stage("train", self._train_pass, **{k: batch.get(k) for k in keys})
+        if self.world > 1:
+            self._dp.allreduce_flat_(self.flat.g, 64 << 20, self.pg)
+        self.opt.step(max_norm=self.grad_clip, use_mask=False, ema=self.shadow, ema_decay=self.mu if self.mu is not None else 0.0, ema_mode=2)
+        self._weights_updated()
+        return {"loss": loss}
+
     def sampler(self, **kwargs):
         """A DDPMSampler over the LIVE model and this runner's schedule (keywords: DDPMSampler's).  Sampling between two ``step`` calls
         leaves the next step as it would have been, with ``use_graphs`` or without: no dropout draw, no change of mode, and the model's
