@@ -293,7 +293,7 @@ int sfron_fp8_update_scales(uint32_t* amax_bits, int n_tensors, float* scales, v
  * quantised at site 0 = sfron_ln_modulate_fwd_q's output, 1 = sfron_cast_e4m3, 2 = the e4m3 GELU output of sfron_fp8_gemm (c_e4m3).  The
  * conversion saturates at 448: a value above it means values WERE clipped (the reference has no fp8 path: nothing there to mirror).  The
  * three words are the CALLER's (round 6): a zero-initialised DEVICE uint32 [3] handed as `act_amax` to every quantising entry point
- * (sfron_ln_modulate_fwd_q, sfron_cast_e4m3, sfron_fp8_gemm_desc.act_amax, sfron_dit_forward_fp8; NULL there = no tracking); this call
+ * (sfron_ln_modulate_fwd_q, sfron_cast_e4m3, sfron_fp8_gemm_desc.act_amax, sfron_dit_fp8_operands.act_amax; NULL there = no tracking); this call
  * copies them to the host (synchronises `stream`) and, with reset != 0, clears them. */
 int sfron_fp8_activation_amax(uint32_t* act_amax, float* out3 /* HOST out, 3 floats */, int reset, void* stream);
 
@@ -781,76 +781,96 @@ typedef struct sfron_dit_cfg {
 int sfron_dit_param_layout(const sfron_dit_cfg* cfg, int64_t* out, int n_out);
 int64_t sfron_dit_workspace_bytes(const sfron_dit_cfg* cfg);   /* < 0 on unsupported cfg */
 
-/* out [B][out_channels][S][S] fp32 = DiT(x_t, t, y); drop [B] uint8 (1 = replace label by the null class) or NULL.
- * Saves activations in `workspace` for sfron_dit_backward. */
-int sfron_dit_forward(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                      const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out, void* stream);
-/* sfron_dit_forward_probed whose block l first waits (hipStreamWaitEvent on `stream`) for block_ready[l] (hipEvent_t, [depth], NULL
- * entries skipped): the optimizer sweep of the previous stage may still be rewriting the LATER blocks' weights on another stream
- * while the first blocks already run (DiT/forget.py:299 -> :310: the remain forward needs block l's new weights only at block l). */
-int sfron_dit_forward_after(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* const* block_ready, void* probe, void* stream);
-/* Config 5: the same forward pass with the four block GEMMs on the fp8 matrix core.  params_e4m3: e4m3 shadow arena (same offsets as
- * params); w_scales: DEVICE fp32 [depth][4] = quantisation scales of {qkv, proj, fc1, fc2}.weight of each block; act_scales: HOST
- * fp32 [3] = static scales of {LayerNorm+modulate output, attention output, gelu(fc1)}; workspace_e4m3: sfron_dit_fp8_workspace_bytes.
- * Saves the same bf16 activations as sfron_dit_forward, so sfron_dit_backward follows unchanged (straight-through estimator).
- * Returns SFRON_ERR_UNSUPPORTED when a block GEMM shape is not a multiple of the fp8 tile (sfron_fp8_gemm_supported). */
+/* Config 5 operands of the forward pass: the four block GEMMs on the fp8 matrix core.  params_e4m3: e4m3 shadow arena (same offsets as
+ * params); w_scales: DEVICE fp32 [depth][4] = quantisation scales of {qkv, proj, fc1, fc2}.weight of each block; act_scales: static scales
+ * of {LayerNorm+modulate output, attention output, gelu(fc1)}, by value, all three > 0; act_amax: the caller's activation-range words
+ * (sfron_fp8_activation_amax), NULL = no tracking; workspace_e4m3: sfron_dit_fp8_workspace_bytes. */
 int64_t sfron_dit_fp8_workspace_bytes(const sfron_dit_cfg* cfg);
-int sfron_dit_forward_fp8(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                          const float* w_scales, const float* act_scales, uint32_t* act_amax /* DEVICE [3] or NULL */, const float* x_t,
-                          const int64_t* t, const int64_t* y,
-                          const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out,
-                          void* const* block_ready /* as sfron_dit_forward_after, or NULL */, void* stream);
-/* The forward pass in two calls (round 6).  phase 1 = only what stands in front of block 0 -- patch embedding, timestep / label embedders,
- * the adaLN modulation of every block: the "conditioning prologue", a chain of ten small dependent launches; phase 2 = only the blocks and
- * the final layer, on the workspace the phase-1 call filled (same arguments).  A caller whose optimizer sweep of the block ranges runs beside
- * the pass on another stream (block_ready) starts that sweep BETWEEN the two calls: beside a bandwidth-heavy sweep every boundary between two
- * small dependent launches costs 60-100 us instead of ~5 (profiles/r06_stage_boundary.txt).  phase 1 ignores block_ready / probe / out.
- * phase 3 = phase 1 without its last launch -- the adaLN product silu(c) W_ada^T + b, the only launch in front of block 0 that reads the
- * adaLN_modulation matrix (DiT/models.py:113-116,119) -- and phase 4 = that launch alone (ABI 16): a caller whose optimizer sweep of that
- * matrix runs on another stream issues phase 3 beside it, orders `stream` behind the sweep, then phase 4 and phase 2. */
-int sfron_dit_forward_phase(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* const* block_ready /* or NULL */, void* probe /* or NULL */, int phase /* 1 | 2 | 3 | 4 */, void* stream);
-int sfron_dit_forward_fp8_phase(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                                const float* w_scales, const float* act_scales, uint32_t* act_amax /* DEVICE [3] or NULL */, const float* x_t,
-                          const int64_t* t, const int64_t* y,
-                                const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out,
-                                void* const* block_ready /* or NULL */, int phase /* 1 | 2 | 3 | 4 */, void* stream);
-/* Same as sfron_dit_forward, with HIP events recorded (on `stream`) around the fc1 GEMM of block 0 -- the
- * dominant kernel class -- into `probe` (may be NULL).  Used by bench.py for the live roofline measurement. */
-int sfron_dit_forward_probed(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                             const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                             void* probe, void* stream);
+typedef struct sfron_dit_fp8_operands {
+  const uint8_t* params_e4m3;
+  const float* w_scales;       /* DEVICE [depth][4] */
+  float act_scales[3];
+  uint32_t* act_amax;          /* DEVICE [3] or NULL */
+  void* workspace_e4m3;
+} sfron_dit_fp8_operands;
+
+/* `phase` of sfron_dit_fwd */
+enum { SFRON_DIT_PASS_WHOLE = 0,             /* prologue + blocks + final layer */
+       SFRON_DIT_PASS_PROLOGUE = 1,          /* everything in front of block 0 */
+       SFRON_DIT_PASS_BLOCKS = 2,            /* blocks + final layer on a workspace a prologue filled */
+       SFRON_DIT_PASS_PROLOGUE_NO_ADA = 3,   /* prologue without the adaLN product */
+       SFRON_DIT_PASS_ADA = 4 };             /* the adaLN product alone */
+
+/* One forward pass: out [B][out_channels][S][S] fp32 = DiT(x_t, t, y).  Saves activations in `workspace` for sfron_dit_backward -- the same
+ * bf16 activations with and without `fp8`, so the backward pass follows unchanged (straight-through estimator).  params, params_bf16, x_t,
+ * t, y, workspace and out must be set in every phase; everything is checked before the first launch (SFRON_ERR_ARG). */
+typedef struct sfron_dit_fwd {
+  const sfron_dit_cfg* cfg;
+  const float* params; const uint16_t* params_bf16;
+  void* workspace;               /* sfron_dit_workspace_bytes */
+  const float* x_t; const int64_t* t; const int64_t* y;
+  const uint8_t* drop;           /* [B] uint8 (1 = replace label by the null class) or NULL */
+  float* out;
+  /* hipEvent_t [depth], NULL entries skipped, or NULL: block l first waits (hipStreamWaitEvent on `stream`) for block_ready[l].  The
+   * optimizer sweep of the previous stage may still be rewriting the LATER blocks' weights on another stream while the first blocks already
+   * run (DiT/forget.py:299 -> :310: the remain forward needs block l's new weights only at block l). */
+  void* const* block_ready;
+  /* sfron_probe_create, or NULL: HIP events recorded (on `stream`) around the fc1 GEMM of block 0 -- the dominant kernel class -- for
+   * bench.py's live roofline measurement.  With `fp8` set nothing is recorded into it. */
+  void* probe;
+  /* SFRON_DIT_PASS_*: the pass in several calls with the same descriptor (round 6).  PROLOGUE = only what stands in front of block 0 --
+   * patch embedding, timestep / label embedders, the adaLN modulation of every block: the "conditioning prologue", a chain of ten small
+   * dependent launches; BLOCKS = only the blocks and the final layer, on the workspace the PROLOGUE call filled.  A caller whose optimizer
+   * sweep of the block ranges runs beside the pass on another stream (block_ready) starts that sweep BETWEEN the two calls: beside a
+   * bandwidth-heavy sweep every boundary between two small dependent launches costs 60-100 us instead of ~5
+   * (profiles/r06_stage_boundary.txt).  PROLOGUE_NO_ADA = PROLOGUE without its last launch -- the adaLN product silu(c) W_ada^T + b, the only
+   * launch in front of block 0 that reads the adaLN_modulation matrix (DiT/models.py:113-116,119) -- and ADA = that launch alone (ABI 16): a
+   * caller whose optimizer sweep of that matrix runs on another stream issues PROLOGUE_NO_ADA beside it, orders `stream` behind the sweep,
+   * then ADA and BLOCKS.  The phases that stop in front of block 0 (PROLOGUE, PROLOGUE_NO_ADA, ADA) ignore block_ready, probe and out.
+   * Same workspace, same results as WHOLE. */
+  int phase;
+  /* NULL = bf16 block GEMMs.  Set: SFRON_ERR_UNSUPPORTED when a block GEMM shape is not a multiple of the fp8 tile
+   * (sfron_fp8_gemm_supported). */
+  const sfron_dit_fp8_operands* fp8;
+} sfron_dit_fwd;
+int sfron_dit_forward(const sfron_dit_fwd* pass, void* stream);
 int sfron_probe_create(int max_samples, void** probe /* HOST out */);
 int sfron_probe_reset(void* probe);
 int sfron_probe_read(void* probe, int* n_samples, double* total_ms);   /* synchronises on the recorded events */
 int sfron_probe_destroy(void* probe);
-/* grads (arena layout, trainable part fully overwritten) = d loss / d params given d_out = d loss / d out.
- * aux (from sfron_aux_create, may be NULL): a side HIP stream + events; the weight-gradient GEMMs and bias column
- * sums then run concurrently with the dgrad / elementwise chain and join `stream` before the call's work ends. */
-int sfron_dit_backward(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* d_out,
-                       const int64_t* y, const uint8_t* drop, void* workspace, float* grads, void* aux, void* stream);
-/* Data-parallel form of the backward pass.  block_events: L hipEvent_t handles (entries may be NULL), event l is recorded on the
- * aux handle's weight-gradient stream once every gradient inside block l's arena range is final except proj.bias and fc2.bias;
- * late_bias: fp32 [L][2][D] that receives those two instead of the arena.  The host can then all-reduce block ranges while the
- * backward pass is still running, all-reduce late_bias and the non-block ranges at the end, and call
- * sfron_dit_scatter_late_bias to put the reduced biases into the arena.  ada_dmod_out / ada_sc_out (both or neither): the
- * adaLN_modulation weight gradient (all blocks + final layer, [(6L+2)D][D], a third of the arena) is NOT computed; instead its two
- * bf16 factors dmod [B][(6L+2)D] and silu(c) [B][D] are copied out, so that the host all-gathers them over the ranks and forms
- * dmod_all^T silu(c)_all with one sfron_gemm_bf16 over the global batch.  (Reference: nn.DataParallel reduces after
- * loss.backward(), DiT/forget.py:193,288.) */
-int sfron_dit_backward_dp(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* d_out,
-                          const int64_t* y, const uint8_t* drop, void* workspace, float* grads, void* aux,
-                          void* const* block_events, float* late_bias, uint16_t* ada_dmod_out, uint16_t* ada_sc_out, void* stream);
+
+/* One backward pass over the workspace a forward pass filled: grads (arena layout, trainable part fully overwritten) = d loss / d params
+ * given d_out = d loss / d out.  (Reference: autograd's loss.backward(), DiT/forget.py:288.) */
+typedef struct sfron_dit_bwd {
+  const sfron_dit_cfg* cfg;
+  const float* params; const uint16_t* params_bf16;
+  void* workspace;
+  const float* d_out; const int64_t* y;
+  const uint8_t* drop;           /* as in the forward pass, or NULL */
+  float* grads;
+  /* from sfron_aux_create, or NULL: a side HIP stream + events; the weight-gradient GEMMs and bias column sums then run concurrently with
+   * the dgrad / elementwise chain and join `stream` before the call's work ends. */
+  void* aux;
+  /* Data-parallel form (either may be NULL; block_events needs aux).  block_events: L hipEvent_t handles (entries may be NULL), event l is
+   * recorded on the aux handle's weight-gradient stream once every gradient inside block l's arena range is final except proj.bias and fc2.bias;
+   * late_bias: fp32 [L][2][D] that receives those two instead of the arena.  The host can then all-reduce block ranges while the backward
+   * pass is still running, all-reduce late_bias and the non-block ranges at the end, and call sfron_dit_scatter_late_bias to put the
+   * reduced biases into the arena.  (Reference: nn.DataParallel reduces after loss.backward(), DiT/forget.py:193,288.) */
+  void* const* block_events;
+  float* late_bias;
+  /* Both or neither.  Set: the adaLN_modulation weight gradient (all blocks + final layer, [(6L+2)D][D], a third of the arena) is NOT
+   * computed; instead its two bf16 factors dmod [B][(6L+2)D] and silu(c) [B][D] are copied out, so that the host all-gathers them over the
+   * ranks and forms dmod_all^T silu(c)_all with one sfron_gemm_bf16 over the global batch. */
+  uint16_t* ada_dmod_out; uint16_t* ada_sc_out;
+} sfron_dit_bwd;
+int sfron_dit_backward(const sfron_dit_bwd* pass, void* stream);
 int sfron_dit_scatter_late_bias(const sfron_dit_cfg* cfg, const float* late_bias, float* grads, void* stream);
 int sfron_aux_create(void** aux /* HOST out */);
 /* attach a probe (sfron_probe_create; NULL detaches): the backward pass then records an event pair on the weight-gradient
  * stream around each of the four weight-gradient GEMMs (qkv, proj, fc1, fc2) of every 9th block -- the kernel that holds the
  * largest share of GPU time -- for bench.py's live roofline figure */
 int sfron_aux_set_probe(void* aux, void* probe);
-/* One-shot: the NEXT sfron_dit_backward / _dp call through this handle also leaves the masked sum of squares of every block weight gradient
+/* One-shot: the NEXT sfron_dit_backward call through this handle also leaves the masked sum of squares of every block weight gradient
  * (qkv / proj / fc1 / fc2 weights of all blocks) in `partials` -- fp64 [sfron_dit_sumsq_partials_len(cfg)], one per 192 x 192 output tile, every
  * entry rewritten by the pass -- taken from the accumulators of the weight-gradient GEMMs (sfron_gemm_desc.sumsq_partials).  mask_arena: byte mask
  * indexed like the parameter / gradient arena (NULL = no mask).  The clip norm of DiT/forget.py:289-298 then needs a pass only over what is left
@@ -860,12 +880,12 @@ int sfron_aux_set_probe(void* aux, void* probe);
 int sfron_dit_sumsq_partials_len(const sfron_dit_cfg* cfg);
 int sfron_aux_arm_sumsq(void* aux, const uint8_t* mask_arena, double* partials);
 /* Orders `stream` behind the point of the LAST backward pass run with this handle after which the adaLN_modulation matrix (weights, bf16
- * shadow) is not read and its gradient factors (sfron_dit_backward_dp: ada_dmod_out / ada_sc_out) are complete: the dgrad through that
+ * shadow) is not read and its gradient factors (sfron_dit_bwd: ada_dmod_out / ada_sc_out) are complete: the dgrad through that
  * Linear.  What remains of the pass is the embedders' backward; the clip norm's share of the adaLN matrix (sfron_sumsq_lowrank) may run
  * beside it on another stream (the host mirror does: -0.12 ms per step; sweeping the matrix itself there measured slower).  No-op before
  * the first backward pass.  Replaces nothing in the reference: scheduling of DiT/forget.py:293-298. */
 int sfron_aux_wait_ada(void* aux, void* stream);
-/* Orders `stream` behind the point of the LAST sfron_dit_backward_dp call with ada_dmod_out / ada_sc_out through this handle at which those two
+/* Orders `stream` behind the point of the LAST sfron_dit_backward call with ada_dmod_out / ada_sc_out through this handle at which those two
  * factors are complete (earlier than sfron_aux_wait_ada: the dgrad through the adaLN Linear is still to come).  sfron_sumsq_lowrank reads
  * nothing else.  No-op before the first such pass. */
 int sfron_aux_wait_ada_factors(void* aux, void* stream);
@@ -873,7 +893,7 @@ int sfron_aux_wait_ada_factors(void* aux, void* stream);
  * backward pass -- a gradient exchange, a sweep -- and must pick a stream that does NOT share a hardware queue with these two: the runtime maps
  * streams onto four hardware queues and two streams on one queue serialise (profiles/r06_hw_queues.txt; the host mirror probes: streams.py). */
 int sfron_aux_streams(void* aux, void** side /* HOST out */, void** side2 /* HOST out */);
-/* Arms the handle for the fp8 backward: every sfron_dit_backward / _dp call through it then runs the four dgrads of each block on the fp8
+/* Arms the handle for the fp8 backward: every sfron_dit_backward call through it then runs the four dgrads of each block on the fp8
  * matrix core (sfron_fp8_dgrad) -- dY cast by sfron_cast_mx8 (d_br, d_br2, dqkv) or by the fc2 dgrad's epilogue (d_hpre); the weight
  * gradients keep reading the bf16 tensors.  w8t: the transposed e4m3 shadow of the block weights, indexed like the block range of the arena
  * (matrix j of block l at its arena offset minus the offset of block 0 rounded down to a multiple of 256); w_scales: fp32 [L][4] (qkv, proj, fc1, fc2), the forward pass's
@@ -882,7 +902,7 @@ int sfron_aux_streams(void* aux, void** side /* HOST out */, void** side2 /* HOS
  * do not take. */
 int64_t sfron_dit_fp8_dgrad_workspace_bytes(const sfron_dit_cfg* cfg);
 int sfron_aux_set_fp8_dgrad(void* aux, const uint8_t* w8t, const float* w_scales, void* mx_workspace);
-/* Arms the handle for fp8 weight gradients: every sfron_dit_backward / _dp call through it then forms the qkv, proj, fc1 and fc2 weight
+/* Arms the handle for fp8 weight gradients: every sfron_dit_backward call through it then forms the qkv, proj, fc1 and fc2 weight
  * gradients of each block with sfron_fp8_wgrad -- dY and the forward input X (xmod1 / o / xmod2 / h) cast by sfron_cast_mx8_t on the
  * weight-gradient stream itself, into this handle's workspace (one operand pair per weight-gradient stream: reuse follows that stream's
  * order).  Biases, adaLN, the embedders and the final layer are unchanged.  Independent of the fp8 forward and of the fp8 dgrads.

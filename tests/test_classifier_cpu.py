@@ -167,7 +167,7 @@ _CTYPE = {"const uint8_t*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "f
 
 def test_header_and_ctypes_prototypes_agree(built):
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sfron.h")).read(), flags=re.S)
-    assert built.ABI_VERSION == 16 and built.lib().sfron_abi_version() == 16
+    assert built.ABI_VERSION == 17 and built.lib().sfron_abi_version() == 17
     for name in NEW:
         m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
         assert m, f"{name} is not declared in include/sfron.h"

@@ -238,7 +238,7 @@ def test_load_image_folder(tmp_path):
 def test_prototype_in_header_and_binding_and_abi_stays_16():
     from sfron import _lib
     L = _lib.lib()
-    assert L.sfron_abi_version() == 16 and _lib.ABI_VERSION == 16
+    assert L.sfron_abi_version() == 17 and _lib.ABI_VERSION == 17
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sfron.h")).read(), flags=re.S)
     kinds = {"int64_t": ctypes.c_int64, "int": ctypes.c_int}
     assert getattr(L, NAME) is not None and NAME in _lib.declared_symbols()

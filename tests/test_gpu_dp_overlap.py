@@ -198,10 +198,10 @@ def test_remain_sweep_beside_the_next_step_gives_the_same_state(fp8):
         assert runner.sweep_across_steps is False          # opt-in
         runner.sweep_across_steps = across
         # round 6: the second-stream launches of a beside-forward sweep issued by the forward pass itself, between its conditioning prologue
-        # and block 0 (sfron_dit_forward_phase); the sweep left across the step boundary is handed to the next step's pass or to drain_sweep
+        # and block 0 (sfron_dit_fwd.phase); the sweep left across the step boundary is handed to the next step's pass or to drain_sweep
         runner.defer_sweep_launch = defer
         # round 6 (late): the adaLN matrix's sweep on the sweep stream in front of the block ranges, the next pass's prologue beside it and its
-        # adaLN product behind an event (sfron_dit_forward_phase 3 / 4); one head block, so that a range does go to the second stream at depth 2
+        # adaLN product behind an event (sfron_dit_fwd.phase: SFRON_DIT_PASS_PROLOGUE_NO_ADA, SFRON_DIT_PASS_ADA); one head block, so that a range does go to the second stream at depth 2
         runner.ada_side = ada_side
         if ada_side:
             runner.sweep_beside_head = 1

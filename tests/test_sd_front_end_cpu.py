@@ -290,5 +290,5 @@ def test_header_and_bindings_declare_the_resample_entry():
     res, args = _lib._PROTOS["sfron_image_resample_u8"]
     assert len(params) == len(args) == 15
     assert "sfron_image_resample_u8" in _lib.declared_symbols()
-    assert _lib.ABI_VERSION == 16
+    assert _lib.ABI_VERSION == 17
     assert _lib.ERR_ARG == 1001

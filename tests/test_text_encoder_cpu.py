@@ -174,7 +174,7 @@ def test_header_and_bindings_declare_the_entry_points():
         assert name in _lib.declared_symbols(), name
     m = re.search(r"SFRON_EPI_QUICK_GELU = (\d+)", hdr)
     assert m and int(m.group(1)) == _lib.EPI_QUICK_GELU == 9
-    assert _lib.ABI_VERSION == 16
+    assert _lib.ABI_VERSION == 17
 
 
 # ------------------------------------------------------------------------------------------------ LatentDiffusion.get_learned_conditioning

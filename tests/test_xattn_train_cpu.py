@@ -94,13 +94,13 @@ def test_new_symbols_header_and_ctypes_agree():
     # sfron_xattn_fwd_lse = sfron_xattn_fwd's arguments with lse in front of the stream
     fwd, lse = _lib._PROTOS["sfron_xattn_fwd"][1], _lib._PROTOS["sfron_xattn_fwd_lse"][1]
     assert lse == fwd[:-1] + [ctypes.c_void_p] + fwd[-1:]
-    assert _lib.ABI_VERSION == 16          # additive: the ABI version stays
+    assert _lib.ABI_VERSION == 17          # additive: the ABI version stays
 
 
 def test_library_exports_the_entry_points():
     from sfron import _lib
     L = _lib.lib()
-    assert L.sfron_abi_version() == 16
+    assert L.sfron_abi_version() == 17
     for name in ("sfron_xattn_fwd_lse", "sfron_xattn_bwd_ws_bytes", "sfron_xattn_bwd"):
         assert getattr(L, name) is not None
     # one fp32 slab [2][Lk][hd] per (sample, head, chunk); never more chunks than 64-row tiles, and B H chunks near 1024 when there are more tiles

@@ -14,7 +14,7 @@ class SfronError(RuntimeError):
 
 
 _lib = None
-ABI_VERSION = 16          # == sfron_abi_version() of the library these ctypes structs / prototypes were written for (checked on load)
+ABI_VERSION = 17          # == sfron_abi_version() of the library these ctypes structs / prototypes were written for (checked on load)
 
 _P = c_void_p     # device pointer
 _S = c_void_p     # hipStream_t
@@ -255,14 +255,34 @@ class DitCfg(ctypes.Structure):
                                      "mlp_hidden", "num_classes", "freq_dim", "out_channels")]
 
 
+class DitFp8Operands(ctypes.Structure):
+    """Mirror of sfron_dit_fp8_operands."""
+    _fields_ = [("params_e4m3", c_void_p), ("w_scales", c_void_p), ("act_scales", c_float * 3), ("act_amax", c_void_p),
+                ("workspace_e4m3", c_void_p)]
+
+
+class DitFwd(ctypes.Structure):
+    """Mirror of sfron_dit_fwd."""
+    _fields_ = [("cfg", POINTER(DitCfg)), ("params", c_void_p), ("params_bf16", c_void_p), ("workspace", c_void_p), ("x_t", c_void_p),
+                ("t", c_void_p), ("y", c_void_p), ("drop", c_void_p), ("out", c_void_p), ("block_ready", POINTER(c_void_p)),
+                ("probe", c_void_p), ("phase", c_int), ("fp8", POINTER(DitFp8Operands))]
+
+
+class DitBwd(ctypes.Structure):
+    """Mirror of sfron_dit_bwd."""
+    _fields_ = [("cfg", POINTER(DitCfg)), ("params", c_void_p), ("params_bf16", c_void_p), ("workspace", c_void_p), ("d_out", c_void_p),
+                ("y", c_void_p), ("drop", c_void_p), ("grads", c_void_p), ("aux", c_void_p), ("block_events", POINTER(c_void_p)),
+                ("late_bias", c_void_p), ("ada_dmod_out", c_void_p), ("ada_sc_out", c_void_p)]
+
+
+DIT_PASS_WHOLE, DIT_PASS_PROLOGUE, DIT_PASS_BLOCKS, DIT_PASS_PROLOGUE_NO_ADA, DIT_PASS_ADA = range(5)       # include/sfron.h SFRON_DIT_PASS_*
 DIT_LAYOUT_LEN = 24
 _PROTOS.update({
     "sfron_dit_param_layout": (c_int, [POINTER(DitCfg), POINTER(c_int64), c_int]),
     "sfron_dit_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_dit_sumsq_partials_len": (c_int, [POINTER(DitCfg)]),
-    "sfron_dit_forward": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _S]),
-    "sfron_dit_backward": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _S]),
-    "sfron_dit_backward_dp": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
+    "sfron_dit_forward": (c_int, [POINTER(DitFwd), _S]),
+    "sfron_dit_backward": (c_int, [POINTER(DitBwd), _S]),
     "sfron_dit_scatter_late_bias": (c_int, [POINTER(DitCfg), _P, _P, _S]),
     "sfron_aux_create": (c_int, [POINTER(c_void_p)]),
     "sfron_aux_destroy": (c_int, [c_void_p]),
@@ -272,16 +292,11 @@ _PROTOS.update({
     "sfron_aux_arm_sumsq": (c_int, [c_void_p, _P, _P]),
     "sfron_aux_wait_ada": (c_int, [c_void_p, _S]),
     "sfron_fp8_activation_amax": (c_int, [_P, POINTER(c_float), c_int, c_void_p]),
-    "sfron_dit_forward_probed": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
-    "sfron_dit_forward_after": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
-    "sfron_dit_forward_phase": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _S]),
-    "sfron_dit_forward_fp8_phase": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _S]),
     "sfron_dit_fp8_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_dit_fp8_dgrad_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_aux_set_fp8_dgrad": (c_int, [c_void_p, _P, _P, _P]),
     "sfron_dit_fp8_wgrad_workspace_bytes": (c_int64, [POINTER(DitCfg)]),
     "sfron_aux_set_fp8_wgrad": (c_int, [c_void_p, _P]),
-    "sfron_dit_forward_fp8": (c_int, [POINTER(DitCfg), _P, _P, _P, _P, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P, _S]),
     "sfron_probe_create": (c_int, [c_int, POINTER(c_void_p)]),
     "sfron_probe_reset": (c_int, [c_void_p]),
     "sfron_probe_read": (c_int, [c_void_p, POINTER(c_int), POINTER(c_double)]),

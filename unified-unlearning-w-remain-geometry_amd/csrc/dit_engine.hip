@@ -284,7 +284,7 @@ int sfron_aux_create(void** aux) {
   for (int i = 0; i < 8; ++i)
     if (hipEventCreateWithFlags(&a->consumed[i], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
   if (hipEventCreateWithFlags(&a->done, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-  // second weight-gradient stream: the 36-tile proj weight gradient runs BESIDE the 108-tile qkv one (see dit_backward_impl)
+  // second weight-gradient stream: the 36-tile proj weight gradient runs BESIDE the 108-tile qkv one (see sfron_dit_backward)
   if (reused) {
   } else if (ablate_mask() & 4) {
     int lo = 0, hi = 0;
@@ -439,35 +439,6 @@ static size_t fp8_ws(const Dims& d, char* base, Fp8Ctx* f) {
   return o;
 }
 
-static int dit_forward_impl(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* probe, const Fp8Ctx* f8, void* stream, void* const* block_wait = nullptr, int phase = 0);
-
-int sfron_dit_forward(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                      const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out, void* stream) {
-  return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, nullptr, nullptr, stream);
-}
-
-int sfron_dit_forward_probed(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                             const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                             void* probe, void* stream) {
-  return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, probe, nullptr, stream);
-}
-
-int sfron_dit_forward_after(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* const* block_ready, void* probe, void* stream) {
-  SFRON_CHECK_ARG(block_ready);
-  return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, probe, nullptr, stream, block_ready);
-}
-
-int sfron_dit_forward_phase(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* const* block_ready, void* probe, int phase, void* stream) {
-  SFRON_CHECK_ARG(phase >= 1 && phase <= 4);
-  return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, probe, nullptr, stream, block_ready, phase);
-}
-
 // fp8 dgrads: two MX operands live at a time -- `a` (d_br / d_br2 / dqkv, each consumed by the launch after its cast) and `b` (d_hpre, written
 // by the fc2 dgrad while it reads `a`, consumed by the fc1 dgrad): e4m3 [M][width] + E8M0 [M][width / 32] each
 struct MxWs { uint8_t *a, *a_sc, *b, *b_sc; };
@@ -514,60 +485,45 @@ int64_t sfron_dit_fp8_workspace_bytes(const sfron_dit_cfg* cfg) {
   return (int64_t)fp8_ws(d, nullptr, nullptr);
 }
 
-static int dit_forward_fp8_impl(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                                const float* w_scales, const float* act_scales, uint32_t* act_amax, const float* x_t, const int64_t* t, const int64_t* y,
-                                const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out, void* const* block_ready, int phase,
-                                void* stream);
-int sfron_dit_forward_fp8(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                          const float* w_scales, const float* act_scales, uint32_t* act_amax, const float* x_t, const int64_t* t, const int64_t* y,
-                          const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out, void* const* block_ready, void* stream) {
-  return dit_forward_fp8_impl(cfg, params, params_bf16, params_e4m3, w_scales, act_scales, act_amax, x_t, t, y, drop, workspace, workspace_e4m3, out,
-                              block_ready, 0, stream);
-}
-int sfron_dit_forward_fp8_phase(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                                const float* w_scales, const float* act_scales, uint32_t* act_amax, const float* x_t, const int64_t* t, const int64_t* y,
-                                const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out, void* const* block_ready, int phase,
-                                void* stream) {
-  SFRON_CHECK_ARG(phase >= 1 && phase <= 4);
-  return dit_forward_fp8_impl(cfg, params, params_bf16, params_e4m3, w_scales, act_scales, act_amax, x_t, t, y, drop, workspace, workspace_e4m3, out,
-                              block_ready, phase, stream);
-}
-static int dit_forward_fp8_impl(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const uint8_t* params_e4m3,
-                                const float* w_scales, const float* act_scales, uint32_t* act_amax, const float* x_t, const int64_t* t, const int64_t* y,
-                                const uint8_t* drop, void* workspace, void* workspace_e4m3, float* out, void* const* block_ready, int phase,
-                                void* stream) {
+int sfron_dit_forward(const sfron_dit_fwd* pass, void* stream) {
+  SFRON_CHECK_ARG(pass && pass->cfg);
+  const int phase = pass->phase;
+  SFRON_CHECK_ARG(phase >= SFRON_DIT_PASS_WHOLE && phase <= SFRON_DIT_PASS_ADA);
   Dims d;
-  RUN(make_dims(cfg, d));
-  SFRON_CHECK_ARG(params_e4m3 && w_scales && act_scales && workspace_e4m3);
-  SFRON_CHECK_ARG(act_scales[0] > 0.f && act_scales[1] > 0.f && act_scales[2] > 0.f);
-  if (!sfron_fp8_gemm_supported(d.M, 3 * d.D, d.D) || !sfron_fp8_gemm_supported(d.M, d.D, d.D) || !sfron_fp8_gemm_supported(d.M, d.F, d.D) ||
-      !sfron_fp8_gemm_supported(d.M, d.D, d.F))
-    return SFRON_ERR_UNSUPPORTED;
-  Fp8Ctx f{params_e4m3, w_scales, act_scales[0], act_scales[1], act_scales[2], nullptr, nullptr, nullptr, act_amax};
-  (void)fp8_ws(d, (char*)workspace_e4m3, &f);
-  return dit_forward_impl(cfg, params, params_bf16, x_t, t, y, drop, workspace, out, nullptr, &f, stream, block_ready, phase);
-}
-
-static int dit_forward_impl(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* x_t,
-                            const int64_t* t, const int64_t* y, const uint8_t* drop, void* workspace, float* out,
-                            void* probe, const Fp8Ctx* f8, void* stream, void* const* block_wait, int phase) {
-  Dims d;
-  RUN(make_dims(cfg, d));
-  SFRON_CHECK_ARG(params && params_bf16 && x_t && t && y && workspace && out);
+  RUN(make_dims(pass->cfg, d));
+  Fp8Ctx f{};
+  const Fp8Ctx* const f8 = pass->fp8 ? &f : nullptr;
+  if (const sfron_dit_fp8_operands* o = pass->fp8) {
+    SFRON_CHECK_ARG(o->params_e4m3 && o->w_scales && o->workspace_e4m3);
+    SFRON_CHECK_ARG(o->act_scales[0] > 0.f && o->act_scales[1] > 0.f && o->act_scales[2] > 0.f);
+    if (!sfron_fp8_gemm_supported(d.M, 3 * d.D, d.D) || !sfron_fp8_gemm_supported(d.M, d.D, d.D) || !sfron_fp8_gemm_supported(d.M, d.F, d.D) ||
+        !sfron_fp8_gemm_supported(d.M, d.D, d.F))
+      return SFRON_ERR_UNSUPPORTED;
+    f = Fp8Ctx{o->params_e4m3, o->w_scales, o->act_scales[0], o->act_scales[1], o->act_scales[2], nullptr, nullptr, nullptr, o->act_amax};
+    (void)fp8_ws(d, (char*)o->workspace_e4m3, &f);
+  }
+  const float* const params = pass->params;
+  const float* const x_t = pass->x_t;
+  const int64_t* const t = pass->t; const int64_t* const y = pass->y;
+  const uint8_t* const drop = pass->drop;
+  float* const out = pass->out;
+  void* const* const block_wait = pass->block_ready;
+  void* const probe = f8 ? nullptr : pass->probe;            // config 5 records nothing into the probe
+  SFRON_CHECK_ARG(params && pass->params_bf16 && x_t && t && y && pass->workspace && out);
   const ParamLayout P = make_layout(d);
-  Workspace w = make_ws(d, (char*)workspace);
-  const uint16_t* wb = params_bf16;
+  Workspace w = make_ws(d, (char*)pass->workspace);
+  const uint16_t* wb = pass->params_bf16;
   const int M = d.M, D = d.D, T = d.T, NM = d.NM;
   sfron_gemm_desc g;
 
-  // phase 1 = only what stands in front of block 0 (the conditioning prologue: a chain of ten small dependent launches + the adaLN product),
-  // phase 2 = only the blocks and the final layer on the workspace a phase-1 call filled, 0 = both.  A caller whose optimizer sweep runs
+  // PROLOGUE = only what stands in front of block 0 (the conditioning prologue: a chain of ten small dependent launches + the adaLN product),
+  // BLOCKS = only the blocks and the final layer on the workspace a PROLOGUE call filled, WHOLE = both.  A caller whose optimizer sweep runs
   // beside this pass on another stream starts that sweep BETWEEN the two calls: beside a bandwidth-heavy sweep every boundary between two of
   // the prologue's small launches costs 60-100 us instead of ~5 (profiles/r06_stage_boundary.txt), ~0.5 ms per pass.
-  // phase 3 = phase 1 without its last launch, the adaLN product -- the only launch of the prologue that reads the adaLN matrix; phase 4 = that
-  // launch alone.  A caller whose optimizer sweep of that matrix (a third of the parameters, ~1.1 ms) runs on another stream issues phase 3
-  // beside it, then orders this stream behind the sweep, then phase 4 and phase 2 (engine.forward(ada_ready=...)).
-  if (phase != 2 && phase != 4) {
+  // PROLOGUE_NO_ADA = PROLOGUE without its last launch, the adaLN product -- the only launch of the prologue that reads the adaLN matrix;
+  // ADA = that launch alone.  A caller whose optimizer sweep of that matrix (a third of the parameters, ~1.1 ms) runs on another stream issues
+  // PROLOGUE_NO_ADA beside it, then orders this stream behind the sweep, then ADA and BLOCKS (engine.forward(ada_ready=...)).
+  if (phase != SFRON_DIT_PASS_BLOCKS && phase != SFRON_DIT_PASS_ADA) {
   // x = x_embedder(x) + pos_embed                                        (models.py:240)
   RUN(sfron_patchify(x_t, d.B, d.C, d.S, d.S, d.p, 0, (uint16_t*)w.patches, d.Kp, stream));
   g = fwd_desc(w.patches, wb + P.pe_w, M, D, d.Kp);
@@ -585,12 +541,12 @@ static int dit_forward_impl(const sfron_dit_cfg* cfg, const float* params, const
   // c = t + y_embedder(y); SiLU(c) feeds every adaLN_modulation           (models.py:242-243,114,132)
   RUN(sfron_cond_fwd(w.temb, params + P.table, y, drop, d.ncls, d.B, D, w.c, (uint16_t*)w.sc, stream));
   }
-  if (phase != 2 && phase != 3) {
+  if (phase != SFRON_DIT_PASS_BLOCKS && phase != SFRON_DIT_PASS_PROLOGUE_NO_ADA) {
   g = fwd_desc(w.sc, wb + P.ada_w, d.B, NM, D);
   g.epilogue = SFRON_EPI_F32; g.bias = params + P.ada_b; g.c_f32 = w.mod; g.ldc_f32 = NM;
   RUN(sfron_gemm_bf16(&g, stream));
   }
-  if (phase == 1 || phase == 3 || phase == 4) return SFRON_OK;
+  if (phase != SFRON_DIT_PASS_WHOLE && phase != SFRON_DIT_PASS_BLOCKS) return SFRON_OK;
 
   // x_next = x + gate * (X W^T + b), branch output saved for the backward pass (models.py:120-121): one product with the gated-residual
   // epilogue, or -- few-tile shapes -- a split-K product + its finish kernel
@@ -609,7 +565,7 @@ static int dit_forward_impl(const sfron_dit_cfg* cfg, const float* params, const
   };
   for (int l = 0; l < d.L; ++l) {
     const int64_t pb = P.blocks + (int64_t)l * P.blk_stride;
-    // block l's weights may still be under an optimizer sweep that runs on another stream (sfron_dit_forward_after): wait for ITS event
+    // block l's weights may still be under an optimizer sweep that runs on another stream (sfron_dit_fwd.block_ready): wait for ITS event
     if (block_wait && block_wait[l] && hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)block_wait[l], 0) != hipSuccess)
       return (int)hipGetLastError();
     const float* mod = w.mod + (size_t)l * 6 * D;          // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
@@ -691,20 +647,30 @@ static int dit_forward_impl(const sfron_dit_cfg* cfg, const float* params, const
 // block l that lives in its arena range is final EXCEPT proj.bias / fc2.bias; late_bias (optional, [L][2][D] fp32): where those
 // two go instead of the arena.  Together they let a data-parallel host all-reduce a block's range while the backward pass is
 // still running, and exchange the late biases (plus everything outside the blocks) once at the end.
-static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* d_out,
-                             const int64_t* y, const uint8_t* drop, void* workspace, float* grads, void* aux, void* const* block_events,
-                             float* late_bias, uint16_t* ada_dmod_out, uint16_t* ada_sc_out, void* stream) {
+int sfron_dit_backward(const sfron_dit_bwd* pass, void* stream) {
+  SFRON_CHECK_ARG(pass && pass->cfg);
+  const float* const params = pass->params;
+  const float* const d_out = pass->d_out;
+  const int64_t* const y = pass->y;
+  const uint8_t* const drop = pass->drop;
+  float* const grads = pass->grads;
+  void* const aux = pass->aux;
+  void* const* const block_events = pass->block_events;
+  float* const late_bias = pass->late_bias;
+  uint16_t* const ada_dmod_out = pass->ada_dmod_out; uint16_t* const ada_sc_out = pass->ada_sc_out;
+  SFRON_CHECK_ARG(!block_events || aux);          // the events are recorded on the aux handle's weight-gradient stream
+  SFRON_CHECK_ARG((ada_dmod_out == nullptr) == (ada_sc_out == nullptr));
   Dims d;
-  RUN(make_dims(cfg, d));
-  SFRON_CHECK_ARG(params && params_bf16 && d_out && y && workspace && grads);
+  RUN(make_dims(pass->cfg, d));
+  SFRON_CHECK_ARG(params && pass->params_bf16 && d_out && y && pass->workspace && grads);
   // An event armed for a producing launch (arm() below) must not outlive this call: a RUN(...) that returns early between arm(i) and its
   // launch would leave the thread's slot armed, and the next k_gemm_pipe / k_row_bwd / k_attn_bwd_fused launch of ANY caller on this thread
   // would hand it -- possibly a destroyed event of a closed engine -- to hipExtLaunchKernelGGL.  Cleared on entry and on every exit path.
   (void)sfron_take_stop_event();
   struct DisarmOnExit { ~DisarmOnExit() { (void)sfron_take_stop_event(); } } disarm_on_exit;
   const ParamLayout P = make_layout(d);
-  Workspace w = make_ws(d, (char*)workspace);
-  const uint16_t* wb = params_bf16;
+  Workspace w = make_ws(d, (char*)pass->workspace);
+  const uint16_t* wb = pass->params_bf16;
   const int M = d.M, D = d.D, T = d.T, NM = d.NM, B = d.B;
   const int rpc = sfron_rows_per_chunk(T);
   SFRON_CHECK_ARG(rpc > 0);
@@ -1077,20 +1043,6 @@ static int dit_backward_impl(const sfron_dit_cfg* cfg, const float* params, cons
   g = wgrad_desc(w.d_h1_bf, w.tfreq, B, D, d.fdim, grads + P.t0_w);
   RUN(sfron_gemm_bf16(&g, stream));
   return SFRON_OK;
-}
-
-int sfron_dit_backward(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* d_out,
-                       const int64_t* y, const uint8_t* drop, void* workspace, float* grads, void* aux, void* stream) {
-  return dit_backward_impl(cfg, params, params_bf16, d_out, y, drop, workspace, grads, aux, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-int sfron_dit_backward_dp(const sfron_dit_cfg* cfg, const float* params, const uint16_t* params_bf16, const float* d_out,
-                          const int64_t* y, const uint8_t* drop, void* workspace, float* grads, void* aux,
-                          void* const* block_events, float* late_bias, uint16_t* ada_dmod_out, uint16_t* ada_sc_out, void* stream) {
-  SFRON_CHECK_ARG(!block_events || aux);          // the events are recorded on the aux handle's weight-gradient stream
-  SFRON_CHECK_ARG((ada_dmod_out == nullptr) == (ada_sc_out == nullptr));
-  return dit_backward_impl(cfg, params, params_bf16, d_out, y, drop, workspace, grads, aux, block_events, late_bias, ada_dmod_out,
-                           ada_sc_out, stream);
 }
 
 int sfron_dit_scatter_late_bias(const sfron_dit_cfg* cfg, const float* late_bias, float* grads, void* stream) {

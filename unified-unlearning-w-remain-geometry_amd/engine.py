@@ -348,7 +348,7 @@ class DitEngine:
 
     def forward(self, x_t, t, y, drop=None, out=None, block_ready=None, between=None, ada_ready=None):
         """block_ready: ctypes array of depth hipEvent_t handles -- block l waits for entry l before it touches its weights.
-        between (with block_ready): a callable run BETWEEN the conditioning prologue and block 0 (sfron_dit_forward_phase): the runner starts
+        between (with block_ready): a callable run BETWEEN the conditioning prologue and block 0 (sfron_dit_fwd.phase): the runner starts
         the block sweep that goes beside this pass there -- behind the prologue's chain of small launches, not beside it (step.py).
         ada_ready (with block_ready): a torch event behind the optimizer sweep of the adaLN matrix, which the runner put on the sweep stream
         (FlatAdam.step(split[ada_side])): everything in front of the adaLN product is issued first -- it runs beside that sweep --, then this
@@ -362,36 +362,21 @@ class DitEngine:
             self.drain_sweep()                 # a block sweep may still be rewriting the weights on its own stream (step.py)
         if ada_ready is not None:
             assert block_ready is not None
-        if between is not None or ada_ready is not None:
-            L, f = _lib.lib(), self.fp8
-            for phase in ((1, 2) if ada_ready is None else (3, 4, 2)):
-                if phase == 4:
-                    torch.cuda.current_stream().wait_event(ada_ready)
-                if f is None:
-                    check(L.sfron_dit_forward_phase(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(x_t), ptr(t), ptr(y),
-                                                    ptr(drop), ptr(self.workspace), ptr(out), block_ready, self.probe, phase, stream_ptr()),
-                          "dit_forward_phase")
-                else:
-                    check(L.sfron_dit_forward_fp8_phase(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(f["w8"]),
-                                                        ptr(f["scales"]), f["act"], ptr(f["act_amax"]), ptr(x_t), ptr(t), ptr(y), ptr(drop), ptr(self.workspace),
-                                                        ptr(f["ws"]), ptr(out), block_ready, phase, stream_ptr()), "dit_forward_fp8_phase")
-                if phase in (1, 4) and between is not None:
-                    between()
-            return out
-        if block_ready is not None and self.fp8 is None:
-            check(_lib.lib().sfron_dit_forward_after(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(x_t), ptr(t), ptr(y),
-                                                     ptr(drop), ptr(self.workspace), ptr(out), block_ready, self.probe, stream_ptr()),
-                  "dit_forward_after")
-            return out
-        if getattr(self, "fp8", None) is not None:
-            f = self.fp8
-            check(_lib.lib().sfron_dit_forward_fp8(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(f["w8"]),
-                                                   ptr(f["scales"]), f["act"], ptr(f["act_amax"]), ptr(x_t), ptr(t), ptr(y), ptr(drop), ptr(self.workspace),
-                                                   ptr(f["ws"]), ptr(out), block_ready, stream_ptr()), "dit_forward_fp8")
-            return out
-        check(_lib.lib().sfron_dit_forward_probed(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(x_t),
-                                                  ptr(t), ptr(y), ptr(drop), ptr(self.workspace), ptr(out), self.probe,
-                                                  stream_ptr()), "dit_forward")
+        f = getattr(self, "fp8", None)
+        fp8 = None if f is None else _lib.DitFp8Operands(ptr(f["w8"]), ptr(f["scales"]), f["act"], ptr(f["act_amax"]), ptr(f["ws"]))
+        d = _lib.DitFwd(ctypes.pointer(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(self.workspace), ptr(x_t), ptr(t), ptr(y),
+                        ptr(drop), ptr(out), block_ready, self.probe, fp8=None if fp8 is None else ctypes.pointer(fp8))
+        if ada_ready is not None:
+            phases = (_lib.DIT_PASS_PROLOGUE_NO_ADA, _lib.DIT_PASS_ADA, _lib.DIT_PASS_BLOCKS)
+        else:
+            phases = (_lib.DIT_PASS_WHOLE,) if between is None else (_lib.DIT_PASS_PROLOGUE, _lib.DIT_PASS_BLOCKS)
+        for phase in phases:                   # the pointers do not change between the phases of one pass
+            if phase == _lib.DIT_PASS_ADA:
+                torch.cuda.current_stream().wait_event(ada_ready)
+            d.phase = phase
+            check(_lib.lib().sfron_dit_forward(ctypes.byref(d), stream_ptr()), f"dit_forward (phase {phase})")
+            if phase in (_lib.DIT_PASS_PROLOGUE, _lib.DIT_PASS_ADA) and between is not None:
+                between()
         return out
 
     # ------------------------------------------------------------------ roofline probe (bench.py)
@@ -440,11 +425,8 @@ class DitEngine:
     def backward_dp(self, d_out, y, drop=None):
         """Backward pass that records per-block completion events and parks proj.bias / fc2.bias gradients in ``late_bias``."""
         self.dp_setup()
-        self._before_backward()
-        check(_lib.lib().sfron_dit_backward_dp(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out), ptr(y),
-                                               ptr(drop), ptr(self.workspace), ptr(self.grads), self.aux, self._dp_handles,
-                                               ptr(self.late_bias), ptr(self.ada_dmod), ptr(self.ada_sc), stream_ptr()), "dit_backward_dp")
-        return self.grads
+        return self._backward(d_out, y, drop, self.grads, "dit_backward (data parallel)", block_events=self._dp_handles,
+                              late_bias=ptr(self.late_bias), ada_dmod_out=ptr(self.ada_dmod), ada_sc_out=ptr(self.ada_sc))
 
     def backward_factored_ada(self, d_out, y, drop=None):
         """Backward pass that does NOT form the adaLN_modulation weight gradient (a [(6L+2)D][D] fp32 matrix, a third of the arena):
@@ -455,10 +437,7 @@ class DitEngine:
             self._ada_f = (torch.empty(self.cfg.batch, NM, dtype=torch.bfloat16, device=self.device),
                            torch.empty(self.cfg.batch, self.cfg.hidden, dtype=torch.bfloat16, device=self.device))
         dmod, sc = self._ada_f
-        self._before_backward()
-        check(_lib.lib().sfron_dit_backward_dp(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out), ptr(y),
-                                               ptr(drop), ptr(self.workspace), ptr(self.grads), self.aux, None, None, ptr(dmod), ptr(sc),
-                                               stream_ptr()), "dit_backward (factored adaLN gradient)")
+        self._backward(d_out, y, drop, self.grads, "dit_backward (factored adaLN gradient)", ada_dmod_out=ptr(dmod), ada_sc_out=ptr(sc))
         return dict(lo=self.layout["ada_w"], NM=dmod.shape[1], D=self.cfg.hidden, dmod=dmod, sc=sc, R=self.cfg.batch, wait=self.ada_wait,
                     wait_factors=self.ada_wait_factors, beside=self.side_streams())
 
@@ -531,9 +510,13 @@ class DitEngine:
         check(_lib.lib().sfron_dit_scatter_late_bias(ctypes.byref(self.cfg), ptr(self.late_bias), ptr(self.grads), stream_ptr()),
               "dit_scatter_late_bias")
 
-    def backward(self, d_out, y, drop=None, grads=None):
-        g = self.grads if grads is None else grads
+    def _backward(self, d_out, y, drop, grads, what, **dp):
+        """One sfron_dit_backward call into ``grads``; dp: the data-parallel fields of sfron_dit_bwd (block_events, late_bias, ada_*_out)."""
         self._before_backward()
-        check(_lib.lib().sfron_dit_backward(ctypes.byref(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(d_out),
-                                            ptr(y), ptr(drop), ptr(self.workspace), ptr(g), self.aux, stream_ptr()), "dit_backward")
-        return g
+        d = _lib.DitBwd(ctypes.pointer(self.cfg), ptr(self.params), ptr(self.params_bf16), ptr(self.workspace), ptr(d_out), ptr(y),
+                        ptr(drop), ptr(grads), self.aux, **dp)
+        check(_lib.lib().sfron_dit_backward(ctypes.byref(d), stream_ptr()), what)
+        return grads
+
+    def backward(self, d_out, y, drop=None, grads=None):
+        return self._backward(d_out, y, drop, self.grads if grads is None else grads, "dit_backward")

@@ -85,7 +85,7 @@ class DiTSFRon:
         self.defer_sweep_launch = False
         # True: a beside-forward sweep also takes the adaLN matrix (a third of the parameters) to the sweep stream, in front of the block ranges,
         # at full grid; the head ranges, the next pass's noising and its conditioning prologue (~20 small launches) run beside it and the pass
-        # waits for it in front of its adaLN product (sfron_dit_forward_phase 3 / 4).  Same kernels on the same operands: bit-identical.
+        # waits for it in front of its adaLN product (sfron_dit_fwd.phase: SFRON_DIT_PASS_PROLOGUE_NO_ADA, SFRON_DIT_PASS_ADA).  Same kernels on the same operands: bit-identical.
         # One box, alternating, six pairs: -0.17 ... -0.32 ms per step (profiles/r06_ab_log.txt).
         self.ada_side = True
         # single-process runs: the forget stage's clip norm (forget.py:293-298) is taken where the gradients are produced -- the block
