@@ -510,7 +510,8 @@ int sfron_rows_to_image_u8(const float* rows, int ld, int B, int H, int W, int m
 int sfron_groupnorm_fwd(const float* x, int ldx, const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps,
                         int swish, const uint8_t* drop_mask, float drop_scale, uint16_t* y, float* mean, float* rstd,
                         void* scratch /* sfron_groupnorm_scratch_bytes(), 16-B aligned; NULL = per-(sample, group) kernels */, void* stream);
-/* dy fp32 [B * HW][C] = gradient wrt y; dx (+)= gradient wrt x; part_gamma / part_beta [B][C] per-sample partial sums */
+/* dy fp32 [B * HW][C] = gradient wrt y; dx (+)= gradient wrt x; part_gamma / part_beta [B][C] per-sample partial sums.  x rows ldx >= C
+ * and dx rows lddx >= C elements apart, in every backward entry point below (SFRON_ERR_ARG otherwise, before any launch) */
 int sfron_groupnorm_bwd(const float* dy, const float* x, int ldx, const float* gamma, const float* beta, const float* mean,
                         const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
                         float* dx, int lddx, int accumulate, float* part_gamma, float* part_beta, void* scratch, void* stream);

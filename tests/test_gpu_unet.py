@@ -124,11 +124,15 @@ def test_conv3x3_forward_dgrad_wgrad(form):
                                              (1280, 64, 1, True), (2560, 16, 1, False)])
 def test_groupnorm_swish_dropout_fwd_bwd(C, HW, swish, drop, form):
     """form "rows": the row-coalesced two-phase kernels (scratch given); "slabs": the per-(sample, group) kernels (no scratch); "rows64": batch 64,
-    where the rule takes the one-launch form (k_gn3_*: a workgroup per sample and block of whole groups; round 6) for every shape here.
+    where the rule takes the one-launch form (k_gn3_*: a workgroup per sample and block of whole groups; round 6) with 8 groups per
+    workgroup for every shape here but (320, 1024): its 80-channel blocks exceed the 128 KB slab and are no whole-line runs, so it stays
+    on the two-phase pair (asserted below; the other sub-forms of the one-launch rule are reached in tests/test_gpu_groupnorm.py).
     Channels per group 2 .. 80, including the LDM widths (10, 40, 80: not powers of two) and more than 1024 channels."""
     from sfron import _lib
     from sfron._lib import check, ptr, stream_ptr
     L = _lib.lib()
+    assert L.sfron_groupnorm_one_launch(64, HW, C, 32) == (0 if (C, HW) == (320, 1024) else 1)
+    assert L.sfron_groupnorm_one_launch(3, HW, C, 32) == 0
     g = torch.Generator().manual_seed(C + HW)
     B = 64 if form == "rows64" else 3
     form = "rows" if form == "rows64" else form

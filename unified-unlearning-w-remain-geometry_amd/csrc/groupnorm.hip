@@ -772,6 +772,7 @@ int sfron_groupnorm_bwd_res(const float* dy, const float* x, int ldx, const floa
                             float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma, float* part_beta,
                             void* scratch, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0);
+  SFRON_CHECK_ARG(ldx >= C && lddx >= C);
   SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
   const int cg = C / groups;
   SFRON_CHECK_ARG(cg <= TPB);
@@ -816,7 +817,7 @@ int sfron_groupnorm_bwd_cast(const float* dy, const float* x, int ldx, const flo
                              const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask, float drop_scale,
                              uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* scratch, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && scratch);
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
+  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && ldx >= C && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
   SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)scratch) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 &&
                   (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
   const int nchunk = gn_chunks(B, HW);
@@ -863,6 +864,7 @@ int sfron_groupnorm_bwd_res_src(const sfron_split_src* src, float* dy, const flo
                                 float drop_scale, float* dx, int lddx, int accumulate, const float* extra, int ld_extra, float* part_gamma,
                                 float* part_beta, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && part_gamma && part_beta && groups > 0 && C % groups == 0 && split_src_ok(src, C));
+  SFRON_CHECK_ARG(ldx >= C && lddx >= C);
   SFRON_CHECK_ARG(B > 0 && HW > 0 && gn_fits31(B, HW, ldx) && gn_fits31(B, HW, lddx) && gn_fits31(B, HW, C));
   SFRON_CHECK_ARG(ldx % 4 == 0 && lddx % 4 == 0 && groups <= 64 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 &&
                   (!drop_mask || ((uintptr_t)drop_mask & 3) == 0) && dy != dx);
@@ -879,7 +881,7 @@ int sfron_groupnorm_bwd_cast_src(const sfron_split_src* src, float* dy, const fl
                                  const float* mean, const float* rstd, int B, int HW, int C, int groups, int swish, const uint8_t* drop_mask,
                                  float drop_scale, uint16_t* dx_bf16, float* col_partials, float* part_gamma, float* part_beta, void* stream) {
   SFRON_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx_bf16 && col_partials && part_gamma && part_beta && split_src_ok(src, C));
-  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
+  SFRON_CHECK_ARG(sfron_groupnorm_bwd_cast_ok(ldx, C, groups) && ldx >= C && B > 0 && HW > 0 && gn_fits31(B, HW, ldx));
   SFRON_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)dx_bf16 & 7) == 0 && (!drop_mask || ((uintptr_t)drop_mask & 3) == 0));
   const int gpb = gn3_gpb(B, HW, C, groups);
   if (!gpb) return SFRON_ERR_UNSUPPORTED;
