@@ -1189,6 +1189,39 @@ int sfron_ddpm_batch_u8(const uint8_t* images, const int64_t* labels, int64_t N,
                         const uint8_t* flip, int B, int uniform_deq, const float* u, int gaussian_deq, const float* n, int mode,
                         const float* image_mean, const int64_t* t_half, int T, float* x0, int64_t* c, int64_t* t, void* stream);
 
+/* ------------------------------------------------------------------ FID Inception-v3 and feature statistics (inception.hip)
+ * What the forward pass of the FID Inception-v3 (inception.py) and the Frechet distance (fid.py) need beside sfron_conv_fwd, the batched
+ * GEMM and sfron_relu_rows.  Every entry point: SFRON_ERR_ARG before any launch for a null pointer, a non-positive extent or an operand
+ * of 2 GiB or more; 64-bit element offsets; no allocation, no synchronisation.
+ *
+ * The im2col matrix of a general convolution: bf16 NHWC rows x [B * H * W][ld] (C channels used) -> bf16 rows [B * Ho * Wo][kh * kw * C],
+ * Ho = (H + 2 pad_h - kh) / stride + 1 (Wo alike); columns (i * kw + j) * C .. + C - 1 = pixel (ho * stride + i - pad_h, wo * stride + j -
+ * pad_w), zero outside the image.  Pure data movement: the bits of x.  C % 8 == 0, ld % 8 == 0, x and rows 16-byte aligned, kh, kw <= 7,
+ * stride 1 or 2, pad_h < kh, pad_w < kw. */
+int sfron_patch_rows(const uint16_t* x, int ld, int B, int H, int W, int C, int kh, int kw, int stride, int pad_h, int pad_w, uint16_t* rows,
+                     void* stream);
+/* TF1's legacy tf.image.resize_bilinear(align_corners=False) of uint8 [B][H][W][3] to Ho x Wo, then (v - 128) / 128, as bf16 rows
+ * [B * Ho * Wo][c_pad] (c_pad == 8: channels 0..2, then zeros -- what sfron_patch_rows reads).  src = dst * (in / out) with no half-pixel
+ * offset, lo = floor(src), hi = min(lo + 1, in - 1), frac = src - lo; fp32 throughout, one IEEE operation per step, in this order:
+ *   top = tl + (tr - tl) * fx;  bot = bl + (br - bl) * fx;  v = top + (bot - top) * fy;  y = (v - 128) / 128;  rows = bf16_rne(y). */
+int sfron_resize_tf1_u8(const uint8_t* img, int B, int H, int W, int Ho, int Wo, int c_pad, uint16_t* rows, void* stream);
+/* 3x3 pools over NHWC rows x [B * H * W][ld] (C channels; fp32, or bf16 with x_bf16 != 0) -> y [B * Ho * Wo][ld_out] (fp32, or bf16 with
+ * y_bf16 != 0): ld_out > C writes a column slice of a wider (concatenated) row.  C, ld, ld_out % 4 == 0; fp32 operands 16-byte, bf16
+ * operands 8-byte aligned.
+ *   SFRON_POOL_MAX_S2  MaxPool2d(3, 2): stride 2, no padding, floor mode (H, W >= 3)
+ *   SFRON_POOL_MAX_S1  MaxPool2d(3, 1, 1): padding counts as -inf
+ *   SFRON_POOL_AVG_S1  AvgPool2d(3, 1, 1, count_include_pad=False): the window's in-bounds values summed in fp64, rounded to fp32 once,
+ *                      divided in fp32 by their number (4 in a corner, 6 on an edge, 9 inside) */
+enum { SFRON_POOL_MAX_S2 = 0, SFRON_POOL_MAX_S1 = 1, SFRON_POOL_AVG_S1 = 2 };
+int sfron_pool3(const void* x, int x_bf16, int ld, int B, int H, int W, int C, int kind, void* y, int y_bf16, int ld_out, void* stream);
+/* y[b][c] = (sum over the HW rows of sample b, in row order, in fp32) / HW -> fp32 [B][C]: the same call gives the same bits */
+int sfron_global_avgpool(const void* x, int x_bf16, int ld, int B, int HW, int C, float* y, void* stream);
+/* np.mean(x, axis=0) and np.cov(x, rowvar=False) of fp32 activations x [N][ld] (D columns) in fp64: mu[d] = (sum_n x[n][d]) / N, then
+ * sigma[i][j] = (sum_n (x[n][i] - mu[i]) (x[n][j] - mu[j])) * (1 / (N - 1)) -- two passes, centred, numpy's reciprocal factor.  Every
+ * output element has one owning thread that adds its terms in a fixed order: the same call gives the same bits; sigma is symmetric bit
+ * for bit.  N >= 2, D % 4 == 0, D <= 2048, ld % 4 == 0, x 16-byte aligned; mu fp64 [D] and sigma fp64 [D][D] are both written. */
+int sfron_feature_stats(const float* x, int64_t N, int D, int ld, double* mu, double* sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

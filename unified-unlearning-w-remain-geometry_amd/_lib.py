@@ -363,6 +363,14 @@ _PROTOS.update({           # csrc/plms.hip: the ldm PLMS sampler
     "sfron_plms_cfg_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _S]),
     "sfron_inpaint_blend": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, c_float, c_float, _P, _S]),
 })
+_PROTOS.update({           # csrc/inception.hip: the FID Inception-v3 and the feature statistics
+    "sfron_patch_rows": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _S]),
+    "sfron_resize_tf1_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _S]),
+    "sfron_pool3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _S]),
+    "sfron_global_avgpool": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _S]),
+    "sfron_feature_stats": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _S]),
+})
+POOL_MAX_S2, POOL_MAX_S1, POOL_AVG_S1 = range(3)           # include/sfron.h SFRON_POOL_*
 PLMS_ORDER1, PLMS_ORDER2, PLMS_ORDER3, PLMS_ORDER4, PLMS_MEAN = range(5)       # include/sfron.h SFRON_PLMS_*
 ERR_ARG = 1001                  # SFRON_ERR_ARG
 ERR_UNSUPPORTED = 1002         # SFRON_ERR_UNSUPPORTED (csrc/common.h)
