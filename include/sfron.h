@@ -1222,6 +1222,45 @@ int sfron_global_avgpool(const void* x, int x_bf16, int ld, int B, int HW, int C
  * for bit.  N >= 2, D % 4 == 0, D <= 2048, ld % 4 == 0, x 16-byte aligned; mu fp64 [D] and sigma fp64 [D][D] are both written. */
 int sfron_feature_stats(const float* x, int64_t N, int D, int ld, double* mu, double* sigma, void* stream);
 
+/* ------------------------------------------------------------------ precision / recall and the Inception Score (manifold.hip)
+ * DDPM/evaluator.py's ManifoldEstimator / DistanceBlock and compute_inception_score over one fp32 NT tile kernel on the exact fp32-input
+ * matrix core instruction.  Every dot product is a blocked sum in one fixed order -- the products of 128 consecutive k are a k-ordered
+ * fmaf chain from 0 (one rounding per product), the block sums are added in block order -- the same order wherever the element falls in
+ * a tile, so the same rows give the same bits at any position, in any batch, and the error is a blocked product's, not a K-long chain's.  Operands are fp32 rows [n][ld] holding D columns:
+ * D % 4 == 0, ld % 4 == 0, ld >= D, 16-byte aligned, under 2 GiB.  Every entry point: SFRON_ERR_ARG before any launch, outputs
+ * untouched, for a null pointer, a misaligned operand, a non-positive extent, an operand of 2 GiB or more or a workspace that is too
+ * small; no allocation, no synchronisation, no scratch.
+ *
+ * C[i][j] = sum_k A[i][k] * B[j][k]: A [M][lda], B [N][ldb], K columns each, C fp32 [M][ldc] (4-byte aligned, ldc >= N, any N). */
+int sfron_gemm_nt_f32(const float* A, int M, int lda, const float* B, int N, int ldb, int K, float* C, int ldc, void* stream);
+/* radii[i][a] = the nhood[a]-th smallest of d(i, .) over ALL N rows, i itself included (its distance is exactly 0):
+ * np.partition(row, arange(kmax + 1))[nhood].  d(i, j) = max((n_i - 2 dot(i, j)) + n_j, 0) in fp32, the reference's fp32 branch, n = the
+ * squared row norm summed in the product's own blocked order (so d(i, i) is exactly 0).  nhood: HOST array of n_nhood (1 .. 4) sizes, each 1 .. 7; N > max(nhood) (np.partition
+ * raises there).  radii fp32 [N][n_nhood].  The N x N matrix is never stored: a query keeps its 8 smallest distances in registers and
+ * only those go through the workspace (sfron_manifold_radii_workspace bytes, 16-byte aligned; contents undefined before and after).
+ * _batched runs the reference's schedule -- queries row_batch at a time against col_batch candidates per launch -- with the same bits
+ * as the one-batch form (a batch size <= 0 or > N means N).  The 2 GiB rule applies to a batch of rows, the operand of a launch: X as a
+ * whole may be larger. */
+int64_t sfron_manifold_radii_workspace(int64_t N, int64_t row_batch, int64_t col_batch);
+int sfron_manifold_radii(const float* X, int64_t N, int D, int ld, const int* nhood, int n_nhood, float* radii, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int sfron_manifold_radii_batched(const float* X, int64_t N, int D, int ld, int64_t row_batch, int64_t col_batch, const int* nhood, int n_nhood,
+                                 float* radii, void* workspace, int64_t workspace_bytes, void* stream);
+/* DistanceBlock.less_thans fused into the tile, set 1 as U: with d(i, j) = max((n1_i - 2 dot) + n2_j, 0),
+ *   in1[i][b] |= any_j d(i, j) <= r2[j][b]      in2[j][a] |= any_i d(i, j) <= r1[i][a]
+ * r1 fp32 [N1][K1], r2 fp32 [N2][K2] (K1, K2 in 1 .. 4; 4-byte aligned), in1 uint8 [N1][K2], in2 uint8 [N2][K1], zeroed by the caller
+ * (or carrying the flags of earlier calls on other row ranges): a flag is only ever turned on, so the result does not depend on order. */
+int sfron_manifold_pr(const float* X1, int64_t N1, const float* r1, int K1, const float* X2, int64_t N2, const float* r2, int K2, int D, int ld1,
+                      int ld2, uint8_t* in1, uint8_t* in2, void* stream);
+/* Per split of split_size rows of logits [N][ld] (C used; the last split may be short), three launches: the rows' softmax in fp32
+ * (exp(x - max) / sum, IN PLACE: logits holds the probabilities afterwards), the column means over the split in fp64, and
+ * scores[s] = exp((1 / n) sum_i sum_c p (log p - log mean_c)) in fp64.  A probability that underflowed to 0 contributes 0, its limit (the
+ * rule of sfron_classify_metrics' entropy; numpy gives NaN there).  scores fp64 [ceil(N / split_size)]; workspace of
+ * sfron_inception_score_workspace bytes, 16-byte aligned.  Fixed summation orders: the same call gives the same bits. */
+int64_t sfron_inception_score_workspace(int64_t N, int C, int split_size);
+int sfron_inception_score(float* logits, int64_t N, int C, int ld, int split_size, double* scores, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -370,6 +370,15 @@ _PROTOS.update({           # csrc/inception.hip: the FID Inception-v3 and the fe
     "sfron_global_avgpool": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _S]),
     "sfron_feature_stats": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _S]),
 })
+_PROTOS.update({           # csrc/manifold.hip: precision / recall manifolds and the Inception Score
+    "sfron_gemm_nt_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _S]),
+    "sfron_manifold_radii_workspace": (c_int64, [c_int64, c_int64, c_int64]),
+    "sfron_manifold_radii": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int64, _S]),
+    "sfron_manifold_radii_batched": (c_int, [_P, c_int64, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, c_int64, _S]),
+    "sfron_manifold_pr": (c_int, [_P, c_int64, _P, c_int, _P, c_int64, _P, c_int, c_int, c_int, c_int, _P, _P, _S]),
+    "sfron_inception_score_workspace": (c_int64, [c_int64, c_int, c_int]),
+    "sfron_inception_score": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _S]),
+})
 POOL_MAX_S2, POOL_MAX_S1, POOL_AVG_S1 = range(3)           # include/sfron.h SFRON_POOL_*
 PLMS_ORDER1, PLMS_ORDER2, PLMS_ORDER3, PLMS_ORDER4, PLMS_MEAN = range(5)       # include/sfron.h SFRON_PLMS_*
 ERR_ARG = 1001                  # SFRON_ERR_ARG

@@ -12,7 +12,8 @@
 The matrix square root of the Frechet distance is ``scipy.linalg.sqrtm`` in fp64 ON THE HOST, as in the reference: that step is not a
 kernel.  Everything before it -- resize, network, statistics -- runs on the device.  No pretrained weights ship with the project: the
 drivers take the path of a checkpoint holding the published ``pt_inception-2015-12-05`` state dict and refuse to run
-without one.  Not built: sFID, Inception Score, precision / recall, data-parallel extraction, fp8.
+without one.  Inception Score, precision and recall over the same feature buffer are evaluator.py.  Not built: sFID, data-parallel
+extraction, fp8.
 """
 import warnings
 
@@ -83,7 +84,8 @@ def feature_statistics(features):
 
 # ------------------------------------------------------------------------------------------------ extraction
 def load_model(checkpoint, device="cuda", **kw):
-    """``inception.InceptionV3`` with the state dict stored at ``checkpoint`` (a torch file; its ``fc.*`` is ignored)."""
+    """``inception.InceptionV3`` with the state dict stored at ``checkpoint`` (a torch file; FID ignores its ``fc.*``, the Inception Score of
+    evaluator.py reads ``fc.weight``)."""
     if not checkpoint:
         raise ValueError("FID needs the Inception checkpoint: pass checkpoint=<path of the pt_inception-2015-12-05 state dict> "
                          "(no pretrained weights ship with this project, see INTEGRATION.md)")

@@ -184,6 +184,7 @@ class InceptionV3(ForwardNet):
         self.max_chunk_bytes = int(max_chunk_bytes)
         self.specs, self.convs, self.stem, self.blocks = inception_plan()
         self._loaded = None
+        self.fc_weight = None        # fp32 [1008][2048] on the device once a state dict with fc.weight is loaded
         self.training = False
 
     def eval(self):
@@ -199,6 +200,7 @@ class InceptionV3(ForwardNet):
 
     # ---------------------------------------------------------------- weights
     def _canonical(self, sd):
+        """-> (the tensors the extractor needs, ``fc.weight`` or None); ``fc.*`` is optional."""
         if "state_dict" in sd and isinstance(sd["state_dict"], dict):
             sd = sd["state_dict"]
         need = [n for n in self.specs if not n.startswith("fc.") and not n.endswith("num_batches_tracked")]
@@ -207,16 +209,18 @@ class InceptionV3(ForwardNet):
         if missing or extra:
             raise KeyError(f"Inception state dict does not match the architecture: missing keys {missing}, unexpected keys {extra}")
         out = OrderedDict()
-        for n in need:
+        for n in need + [n for n in ("fc.weight",) if n in sd]:
             t = torch.as_tensor(sd[n]).detach().cpu()
             if tuple(t.shape) != tuple(self.specs[n]):
                 raise ValueError(f"{n}: shape {tuple(t.shape)}, the architecture needs {tuple(self.specs[n])}")
             out[n] = t.clone()
-        return out
+        return out, out.pop("fc.weight", None)
 
     def load_state_dict(self, sd):
-        """Takes the published file's keys; its ``fc.*`` (the 1008-way head, not used by FID) is ignored."""
-        can = self._canonical(sd)                     # raises before anything touches the GPU
+        """Takes the published file's keys.  ``fc.*`` (the 1008-way head, not used by FID) stays optional; when ``fc.weight`` is there it
+        is kept as an fp32 device tensor [1008][2048] (not cast to bf16) for ``logits``.  ``fc.bias`` is never used: the reference's
+        ``_create_softmax_graph`` multiplies the pooled features by the head's weight matrix (``matmul.inputs[1]``) and adds no bias."""
+        can, fc = self._canonical(sd)                 # raises before anything touches the GPU
         off, index, host = 0, {}, []
 
         def put(name, t):
@@ -250,8 +254,23 @@ class InceptionV3(ForwardNet):
                 fwd = torch.zeros(cout * 9 * cin, dtype=torch.bfloat16, device=self.dev)
                 check(_L().sfron_conv_wprep(self._p(name + ".w"), cout, cin, 9, cout, cin, ptr(fwd), None, stream_ptr()), "conv_wprep")
                 self.conv3[name] = fwd
+        self.fc_weight = None if fc is None else fc.to(torch.float32).contiguous().to(self.dev)
         self._loaded = can
         return self
+
+    def logits(self, features_2048):
+        """The 1008-way head without its bias over pooled features fp32 [n][2048] on the device: sfron_gemm_nt_f32 against ``fc.weight``
+        (exact fp32 products summed in one fixed blocked order per logit) -> fp32 [n][1008]."""
+        if self.fc_weight is None:
+            raise _lib.SfronError("InceptionV3.logits: the loaded state dict has no fc.weight (the Inception Score needs the 1008-way head)")
+        x = features_2048
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 2048 or x.shape[0] < 1:
+            raise _lib.SfronError("InceptionV3.logits takes fp32 [n][2048] features on the GPU (no CPU fallback)")
+        x = x.contiguous()
+        out = torch.empty(x.shape[0], FC_OUT, dtype=torch.float32, device=x.device)
+        guard(x, out)
+        check(_L().sfron_gemm_nt_f32(ptr(x), x.shape[0], 2048, ptr(self.fc_weight), FC_OUT, 2048, 2048, ptr(out), FC_OUT, stream_ptr()), "gemm_nt_f32")
+        return out
 
     def state_dict(self):
         if self._loaded is None:
